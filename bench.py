@@ -18,13 +18,26 @@ rank 0, which merges with the router's semantics (client.go:1497/1558)
 by one sort over world*k keys.
 
 Prints ONE JSON line from rank 0 (driver contract), including the
-roofline of the dominant kernel (the ADC list scan) and the CPU-oracle
-baseline (kind "port") timed on this host.
+roofline of the dominant kernel (the ADC list scan, from the per-step
+HIP-event timings the timed steps record anyway).
+
+A plain run does only what the headline figure needs: set up, warm up,
+time the steps, print the line. --full adds the checks that take runs of
+their own: recall@k against the engine's exact FLAT path, the scanned
+codes/query probe and the CPU-oracle baseline (kind "port") timed on
+this host; without it those fields of the line are null.
+
+--dump-outputs DIR writes what the last timed step returned to its
+caller (DIR/dists.npy float32, DIR/ids.npy float64), so that two builds
+can be compared output for output: data, queries and training are
+seeded, so the same arguments give the same inputs on every run.
 """
 import argparse
 import json
 import os
+import queue
 import sys
+import threading
 import time
 
 # pin this rank's GPU before torch / libgamma load anything
@@ -96,39 +109,101 @@ def log(msg):
         print(f"[bench] {msg}", file=sys.stderr, flush=True)
 
 
-def gen_data(n, d, seed, ncl=10000, sigma=0.10, chunk=1_000_000):
-    """Clustered-Gaussian DB (BASELINE.md protocol), chunked to bound RAM."""
+def gen_data_chunks(out, seed, ncl=10000, sigma=0.10, chunk=1_000_000):
+    """Fill `out` with the clustered-Gaussian DB (BASELINE.md protocol)
+    chunk by chunk; yields (start, end) as each chunk becomes final."""
+    n, d = out.shape
     rng = np.random.default_rng(seed)
     centers = rng.random((ncl, d), dtype=np.float32)
-    out = np.empty((n, d), dtype=np.float32)
     for s in range(0, n, chunk):
         e = min(s + chunk, n)
         asg = rng.integers(0, ncl, size=e - s)
         out[s:e] = centers[asg]
         out[s:e] += sigma * rng.standard_normal((e - s, d),
                                                 dtype=np.float32)
+        yield s, e
+
+
+def gen_data(n, d, seed, ncl=10000, sigma=0.10, chunk=1_000_000):
+    """Clustered-Gaussian DB (BASELINE.md protocol), chunked to bound RAM."""
+    out = np.empty((n, d), dtype=np.float32)
+    for _ in gen_data_chunks(out, seed, ncl, sigma, chunk):
+        pass
     return out
+
+
+def gen_queries(base_full, cfg):
+    rng = np.random.default_rng(43)
+    idx = rng.integers(0, cfg["n"], size=cfg["nq"])
+    return base_full[idx] + 0.05 * rng.standard_normal(
+        (cfg["nq"], cfg["d"]), dtype=np.float32)
+
+
+def index_params(cfg):
+    if cfg["kind"] == "FLAT":
+        return '{"metric_type": "L2"}'
+    return (
+        '{"ncentroids": %d, %s"metric_type": "L2", '
+        '"training_threshold": %d, "bucket_max_size": 12800000}'
+        % (cfg["nlist"],
+           f'"nsubvector": {cfg["m"]}, ' if cfg["kind"] == "IVFPQ"
+           else "",
+           cfg["train_n"]))
 
 
 def build_engine(cfg, base, rank, path=None):
     from vearch_amd import GammaEngine
     eng = GammaEngine(path=path or f"/tmp/gamma_bench_r{rank}")
-    if cfg["kind"] == "FLAT":
-        params = '{"metric_type": "L2"}'
-    else:
-        params = (
-            '{"ncentroids": %d, %s"metric_type": "L2", '
-            '"training_threshold": %d, "bucket_max_size": 12800000}'
-            % (cfg["nlist"],
-               f'"nsubvector": {cfg["m"]}, ' if cfg["kind"] == "IVFPQ"
-               else "",
-               cfg["train_n"]))
-    eng.create_table(cfg["d"], cfg["kind"], params)
+    eng.create_table(cfg["d"], cfg["kind"], index_params(cfg))
     t0 = time.time()
     step = 1_000_000
     for s in range(0, base.shape[0], step):
         eng.add(base[s:s + step])
     log(f"rank{rank}: added {base.shape[0]} vecs in {time.time()-t0:.1f}s")
+    t0 = time.time()
+    eng.build_index()
+    log(f"rank{rank}: build_index in {time.time()-t0:.1f}s")
+    return eng
+
+
+def start_table_producer(cfg):
+    """Start filling the full table on a producer thread, in the same
+    1M-row chunks and from the same random stream as gen_data. Returns
+    (table, queue); the queue yields (start, end) as each chunk becomes
+    final, then None (or the exception that stopped the producer)."""
+    base = np.empty((cfg["n"], cfg["d"]), dtype=np.float32)
+    done = queue.Queue()
+
+    def produce():
+        try:
+            for se in gen_data_chunks(base, seed=42):
+                done.put(se)
+            done.put(None)
+        except BaseException as ex:  # noqa: BLE001
+            done.put(ex)
+
+    threading.Thread(target=produce, daemon=True).start()
+    return base, done
+
+
+def build_engine_streamed(cfg, base, done, rank, path=None):
+    """build_engine with data generation and ingest overlapped: each
+    chunk of the producer's table is added as soon as it is final. The
+    engine sees the same add() calls in the same order as build_engine
+    on the finished table."""
+    from vearch_amd import GammaEngine
+    eng = GammaEngine(path=path or f"/tmp/gamma_bench_r{rank}")
+    eng.create_table(cfg["d"], cfg["kind"], index_params(cfg))
+    t0 = time.time()
+    while True:
+        item = done.get()
+        if item is None:
+            break
+        if isinstance(item, BaseException):
+            raise item
+        eng.add(base[item[0]:item[1]])
+    log(f"rank{rank}: added {base.shape[0]} vecs in {time.time()-t0:.1f}s "
+        "(overlapped with data gen)")
     t0 = time.time()
     eng.build_index()
     log(f"rank{rank}: build_index in {time.time()-t0:.1f}s")
@@ -193,6 +268,29 @@ def cpu_baseline(eng, cfg, queries, budget_s=20.0):
     }
 
 
+DUMP_LIMIT_BYTES = 64 * 1024 * 1024
+
+
+def dump_outputs(out_dir, dists, ids):
+    """Write the (nq, k) result of the last timed step: dists as float32,
+    ids as float64 (exact for any docid below 2^53). Above the size limit
+    a fixed seeded sample of the query rows is written, with the chosen
+    row numbers alongside."""
+    os.makedirs(out_dir, exist_ok=True)
+    dists = np.asarray(dists)
+    ids = np.asarray(ids)
+    row_bytes = dists.shape[1] * (4 + 8) + 8
+    max_rows = DUMP_LIMIT_BYTES // row_bytes
+    if dists.shape[0] > max_rows:
+        rows = np.sort(np.random.default_rng(44).choice(
+            dists.shape[0], size=max_rows, replace=False))
+        dists, ids = dists[rows], ids[rows]
+        np.save(os.path.join(out_dir, "rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "dists.npy"), dists.astype(np.float32))
+    np.save(os.path.join(out_dir, "ids.npy"), ids.astype(np.float64))
+    log(f"wrote {dists.shape[0]} result rows to {out_dir}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -210,8 +308,18 @@ def main():
                          "with it, reference ivfpq.cc:142 nlist*39 rule)")
     ap.add_argument("--rerank", type=int, default=-1,
                     help="recall_num (-1 = workload default)")
-    ap.add_argument("--skip-recall", action="store_true")
-    ap.add_argument("--skip-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checks that take runs of their "
+                         "own: recall@k, scanned codes/query, the "
+                         "CPU-oracle baseline")
+    ap.add_argument("--skip-recall", action="store_true",
+                    help="with --full: leave out the recall check")
+    ap.add_argument("--skip-cpu-baseline", action="store_true",
+                    help="with --full: leave out the CPU-oracle baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last one "
+                         "returned as DIR/dists.npy (float32) and "
+                         "DIR/ids.npy (float64)")
     ap.add_argument("--index-dir", default="",
                     help="reuse a built index: load from DIR if a dump "
                          "exists there, else build and dump to DIR")
@@ -246,8 +354,6 @@ def main():
             torch.cuda.set_device(0)  # HIP_VISIBLE_DEVICES pins the GPU
         dist = tdist
 
-    import torch
-
     idir = args.index_dir
     if idir and world > 1:
         idir = os.path.join(idir, f"r{rank}")
@@ -255,20 +361,20 @@ def main():
         os.path.join(idir, "gamma.dump")) and os.path.exists(
         os.path.join(idir, "queries.npy"))
 
+    # single partition: data generation starts now and runs under the
+    # torch import, the engine start-up and the ingest
+    t_gen = time.time()
+    producer = None
+    if world == 1 and not have_dump:
+        producer = start_table_producer(cfg)
+
+    import torch
+
     if have_dump:
         from vearch_amd import GammaEngine
         t0 = time.time()
         eng = GammaEngine(path=idir)
-        if cfg["kind"] == "FLAT":
-            params = '{"metric_type": "L2"}'
-        else:
-            params = (
-                '{"ncentroids": %d, %s"metric_type": "L2", '
-                '"training_threshold": %d, "bucket_max_size": 12800000}'
-                % (cfg["nlist"],
-                   f'"nsubvector": {cfg["m"]}, ' if cfg["kind"] == "IVFPQ"
-                   else "", cfg["train_n"]))
-        eng.create_table(cfg["d"], cfg["kind"], params)
+        eng.create_table(cfg["d"], cfg["kind"], index_params(cfg))
         eng.load()
         queries = np.load(os.path.join(idir, "queries.npy"))
         cfg["nq"] = queries.shape[0]
@@ -278,19 +384,24 @@ def main():
         # one table of N vectors, sharded round-robin over partitions
         # (shard-local docid * world + rank = global docid); every rank
         # derives the identical query set from the same seeds
-        t0 = time.time()
-        base_full = gen_data(cfg["n"], cfg["d"], seed=42)
-        rng = np.random.default_rng(43)
-        idx = rng.integers(0, cfg["n"], size=cfg["nq"])
-        queries = base_full[idx] + 0.05 * rng.standard_normal(
-            (cfg["nq"], cfg["d"]), dtype=np.float32)
-        base = np.ascontiguousarray(base_full[rank::world])             if world > 1 else base_full
-        del base_full
-        log(f"data gen in {time.time()-t0:.1f}s "
-            f"(shard {base.shape[0]} of {cfg['n']})")
         if idir:
             os.makedirs(idir, exist_ok=True)
-        eng = build_engine(cfg, base, rank, path=idir or None)
+        if world > 1:
+            t0 = time.time()
+            base_full = gen_data(cfg["n"], cfg["d"], seed=42)
+            queries = gen_queries(base_full, cfg)
+            base = np.ascontiguousarray(base_full[rank::world])
+            del base_full
+            log(f"data gen in {time.time()-t0:.1f}s "
+                f"(shard {base.shape[0]} of {cfg['n']})")
+            eng = build_engine(cfg, base, rank, path=idir or None)
+        else:
+            base, done = producer
+            eng = build_engine_streamed(cfg, base, done, rank,
+                                        path=idir or None)
+            log(f"data gen + ingest + build in {time.time()-t_gen:.1f}s")
+            queries = gen_queries(base, cfg)
+        del base
         if idir:
             eng.dump()
             np.save(os.path.join(idir, "queries.npy"), queries)
@@ -304,7 +415,7 @@ def main():
     # so this exceeds nprobe*N/nlist; the roofline stays on algorithmic
     # bytes per BASELINE.md)
     eff_codes = None
-    if rank == 0 and cfg["kind"] in ("IVFPQ", "IVFFLAT"):
+    if args.full and rank == 0 and cfg["kind"] in ("IVFPQ", "IVFFLAT"):
         try:
             from vearch_amd.engine import lib as _lib
             _, pl = eng.debug_coarse_assign(queries[:256], cfg["nprobe"])
@@ -317,7 +428,7 @@ def main():
             pass
 
     recall = None
-    if rank == 0 and not args.skip_recall and world == 1:
+    if args.full and rank == 0 and not args.skip_recall and world == 1:
         t0 = time.time()
         recall = compute_recall(eng, cfg, queries)
         log(f"recall@{cfg['k']} = {recall:.4f} ({time.time()-t0:.1f}s)")
@@ -357,8 +468,9 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t_start = time.time()
+    last = (None, None)
     for _ in range(args.steps):
-        gather_and_merge(*step())
+        last = gather_and_merge(*step())
         scan_ms.append(eng.last_timing()["scan_us"] / 1000.0)
     torch.cuda.synchronize()
     if world > 1:
@@ -370,6 +482,9 @@ def main():
             el = el.cuda()
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
         elapsed = float(el.item())
+
+    if rank == 0 and args.dump_outputs and last[0] is not None:
+        dump_outputs(args.dump_outputs, *last)
 
     if rank == 0:
         qps = cfg["nq"] * args.steps / elapsed
@@ -399,7 +514,7 @@ def main():
                 and not args.nprobe else None,
             }
         cpu = None
-        if not args.skip_cpu_baseline and world == 1:
+        if args.full and not args.skip_cpu_baseline and world == 1:
             try:
                 cpu = cpu_baseline(eng, cfg, queries)
             except Exception as ex:  # noqa: BLE001
