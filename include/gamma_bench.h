@@ -55,7 +55,8 @@ int GammaDebugCoarseAssign(void *engine, int nq, const float *xq, int nprobe,
                            int64_t *out_lists, float *out_dists);
 
 /* Debug: copy the trained model to host: centroids (nlist*d), pq codebooks
- * (M*ksub*dsub). Buffers may be NULL to skip. */
+ * (M*ksub*dsub, ksub = 2^nbits_per_idx: 256 at 8 bits, 16 at 4 bits).
+ * Buffers may be NULL to skip. */
 int GammaDebugGetModel(void *engine, float *centroids, float *codebooks);
 /* OPQ debug hooks (oracle parity chains on the engine's own R and its
  * GPU rotation so downstream ADC stays bit-exact):
@@ -66,7 +67,10 @@ int GammaDebugApplyOPQ(void *engine, const float *xq, int nq, float *out);
 
 /* Debug: fetch the contents of inverted list `list_no`: returns size, and
  * copies ids (int64, with bit-63 delete marks preserved, reference
- * realtime_mem_data.h:26) and codes (size*code_size u8) if non-NULL. */
+ * realtime_mem_data.h:26) and codes (size*code_size u8) if non-NULL.
+ * code_size = M*nbits_per_idx/8. At 8 bits byte m is sub-quantizer m; at
+ * 4 bits entries are packed, byte b = sub-quantizer 2b in bits 0-3 and
+ * 2b+1 in bits 4-7 (the same layout as the device buckets and the dump). */
 int64_t GammaDebugGetList(void *engine, int64_t list_no, int64_t *ids,
                           uint8_t *codes);
 

@@ -285,8 +285,10 @@ int IndexParams::parse(const std::string &json, std::string *err) {
       return -1;
     }
   }
-  if (nbits != 8) {
-    if (err) *err = "only nbits_per_idx=8 supported";
+  if (nbits != 4 && nbits != 8) {
+    if (err)
+      *err = "nbits_per_idx=" + std::to_string(nbits) +
+             " not supported (supported values: 4 and 8)";
     return -1;
   }
   if (v.has("hnsw")) {
@@ -325,7 +327,13 @@ int IVFIndex::init(int d, const IndexParams &p) {
     M_ = p.nsubvector > 0 ? p.nsubvector : d / 2; /* ivfpq.cc:122-124 */
     if (M_ <= 0 || d % M_ != 0 || M_ % 4 != 0) return -1;
     dsub_ = d / M_;
-    code_size_ = M_;
+    /* 4-bit codes pack two sub-quantizers per byte (2b low nibble,
+     * 2b+1 high nibble); M % 4 == 0 keeps the entry size even. OPQ
+     * training runs the unpacked 8-bit encode and is not wired for 4 */
+    if (p.nbits != 4 && p.nbits != 8) return -1;
+    if (p.nbits == 4 && p.has_opq) return -1;
+    ksub_ = 1 << p.nbits;
+    code_size_ = M_ * p.nbits / 8;
   } else {
     M_ = 0;
     dsub_ = 0;
@@ -679,7 +687,7 @@ int IVFIndex::train(const float *xt, int64_t n, hipStream_t s,
     GAMMA_CHECK(hipMemcpy(resid_h.data(), resid.get(), (size_t)n * d_ * 4,
                           hipMemcpyDeviceToHost));
 
-    /* per-subspace k-means, ksub=256, niter=25 (faiss PQ default) */
+    /* per-subspace k-means, ksub=2^nbits, niter=25 (faiss PQ default) */
     std::vector<float> books((size_t)M_ * ksub_ * dsub_);
     std::vector<float> sub((size_t)n * dsub_);
     for (int m = 0; m < M_; m++) {
@@ -700,7 +708,7 @@ int IVFIndex::train(const float *xt, int64_t n, hipStream_t s,
                           (size_t)M_ * ksub_ * dsub_ * 4,
                           hipMemcpyHostToDevice));
     if (btable_.reserve((size_t)nlist_ * M_ * ksub_ * 4)) return -1;
-    if (gk::pq_tables_b(s, d_, M_, nlist_, centroids_.as<float>(),
+    if (gk::pq_tables_b(s, d_, M_, ksub_, nlist_, centroids_.as<float>(),
                         codebooks_.as<float>(),
                         btable_.as<float>()) != hipSuccess)
       return -1;
@@ -772,6 +780,18 @@ int IVFIndex::pq_subspace_kmeans_(const float *sub_host, int64_t n,
                     std::max<int64_t>(counts[c], 1));
   }
   return 0;
+}
+
+/* residuals -> bucket-format entries (code_size_ bytes each) */
+int IVFIndex::encode_entries_(hipStream_t s, int64_t n, const float *resid,
+                              uint8_t *codes) {
+  hipError_t e =
+      ksub_ == 16
+          ? gk::pq_encode_pack4(s, n, d_, M_, resid, codebooks_.as<float>(),
+                                codes)
+          : gk::pq_encode(s, n, d_, M_, ksub_, resid,
+                          codebooks_.as<float>(), codes);
+  return e == hipSuccess ? 0 : -1;
 }
 
 int IVFIndex::update_dev_buckets(hipStream_t s) {
@@ -849,16 +869,14 @@ int IVFIndex::add(const float *x_host, const int64_t *vids, int64_t n,
                         asg.as<int32_t>(), resid.as<float>()) != hipSuccess)
         return -1;
       if (codes.reserve((size_t)cn * code_size_)) return -1;
-      if (gk::pq_encode(s, cn, d_, M_, ksub_, resid.as<float>(),
-                        codebooks_.as<float>(),
-                        codes.as<uint8_t>()) != hipSuccess)
+      if (encode_entries_(s, cn, resid.as<float>(), codes.as<uint8_t>()))
         return -1;
       codes_h.resize((size_t)cn * code_size_);
       (void)hipMemcpy(codes_h.data(), codes.get(), (size_t)cn * code_size_,
                 hipMemcpyDeviceToHost);
       /* per-vector S term against the vector's own list's B table */
       if (sterm.reserve((size_t)cn * 4)) return -1;
-      if (gk::pq_sterm(s, cn, M_, nlist_, codes.as<uint8_t>(),
+      if (gk::pq_sterm(s, cn, M_, ksub_, nlist_, codes.as<uint8_t>(),
                        asg.as<int32_t>(), 0, btable_.as<float>(),
                        sterm.as<float>()) != hipSuccess)
         return -1;
@@ -1027,12 +1045,10 @@ int IVFIndex::prepare_fast_one(const float *vec_h, hipStream_t s,
                       asg.as<int32_t>(), resid.as<float>()) != hipSuccess)
       return -1;
     if (codes.reserve((size_t)code_size_)) return -1;
-    if (gk::pq_encode(s, 1, d_, M_, ksub_, resid.as<float>(),
-                      codebooks_.as<float>(),
-                      codes.as<uint8_t>()) != hipSuccess)
+    if (encode_entries_(s, 1, resid.as<float>(), codes.as<uint8_t>()))
       return -1;
     if (sterm.reserve(4)) return -1;
-    if (gk::pq_sterm(s, 1, M_, nlist_, codes.as<uint8_t>(),
+    if (gk::pq_sterm(s, 1, M_, ksub_, nlist_, codes.as<uint8_t>(),
                      asg.as<int32_t>(), 0, btable_.as<float>(),
                      sterm.as<float>()) != hipSuccess)
       return -1;
@@ -1196,7 +1212,7 @@ int IVFIndex::search(const float *q_dev, int nq, int k2, int nprobe,
     const float *atab = nullptr;
     if (!metric_ip) {
       if (sc.atab.reserve((size_t)nq * M_ * ksub_ * 4)) return -1;
-      GAMMA_CHECK(gk::pq_tables_a(s, nq, d_, M_, q_dev,
+      GAMMA_CHECK(gk::pq_tables_a(s, nq, d_, M_, ksub_, q_dev,
                                   codebooks_.as<float>(),
                                   sc.atab.as<float>()));
       atab = sc.atab.as<float>();
@@ -1241,7 +1257,7 @@ int IVFIndex::search(const float *q_dev, int nq, int k2, int nprobe,
                                  s));
       qmap_dev = sc.qmap.as<int32_t>();
     }
-    GAMMA_CHECK(gk::ivfpq_scan(s, nq, S, d_, M_, nprobe, k2, q_dev,
+    GAMMA_CHECK(gk::ivfpq_scan(s, nq, S, d_, M_, ksub_, nprobe, k2, q_dev,
                                centroids_.as<float>(),
                                codebooks_.as<float>(), atab,
                                sc.pdists.as<float>(),
@@ -1360,7 +1376,7 @@ int IVFIndex::load(FILE *f, hipStream_t s) {
     (void)hipMemcpy(codebooks_.get(), books.data(), books.size() * 4,
               hipMemcpyHostToDevice);
     if (btable_.reserve((size_t)nlist_ * M_ * ksub_ * 4)) return -1;
-    if (gk::pq_tables_b(s, d_, M_, nlist_, centroids_.as<float>(),
+    if (gk::pq_tables_b(s, d_, M_, ksub_, nlist_, centroids_.as<float>(),
                         codebooks_.as<float>(),
                         btable_.as<float>()) != hipSuccess)
       return -1;
@@ -1424,8 +1440,8 @@ int IVFIndex::load(FILE *f, hipStream_t s) {
   trained_ = true;
   if (update_dev_buckets(s)) return -1;
   if (params_.kind == IndexKind::IVFPQ) {
-    if (gk::pq_sterm_buckets(s, nlist_,
-                             M_, dev_buckets_.as<GammaBucketDev>(),
+    if (gk::pq_sterm_buckets(s, nlist_, M_, ksub_,
+                             dev_buckets_.as<GammaBucketDev>(),
                              btable_.as<float>()) != hipSuccess)
       return -1;
     GAMMA_CHECK(hipStreamSynchronize(s));

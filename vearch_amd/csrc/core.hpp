@@ -197,7 +197,7 @@ struct IndexParams {
   IndexKind kind = IndexKind::IVFPQ;
   int ncentroids = 2048;       /* ivfpq.h:1049 default */
   int nsubvector = 0;          /* 0 -> d/2 (ivfpq.cc:122-124) */
-  int nbits = 8;
+  int nbits = 8;               /* nbits_per_idx: 4 or 8 (IVFPQ) */
   int nprobe = 80;
   int bucket_init_size = 1000;
   int bucket_max_size = 1280000;
@@ -301,6 +301,8 @@ class IVFIndex {
   int pq_subspace_kmeans_(const float *sub_host, int64_t n,
                           std::vector<float> &cb, hipStream_t s,
                           int seed_off);
+  int encode_entries_(hipStream_t s, int64_t n, const float *resid,
+                      uint8_t *codes);
   int update_dev_buckets(hipStream_t s);
   /* OPQ-NP training: alternate PQ fit and orthogonal Procrustes
    * (SVD), the algorithm behind faiss OPQMatrix::train (the reference

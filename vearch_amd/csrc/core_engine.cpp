@@ -69,6 +69,13 @@ int Engine::create_table(const std::string &name,
              " not in this build's scope (FLAT/IVFFLAT/IVFPQ)";
     return -1;
   }
+  if (params_.kind == IndexKind::IVFPQ && params_.nbits == 4 &&
+      params_.has_opq) {
+    if (err)
+      *err = "opq with nbits_per_idx=4 is not supported (use "
+             "nbits_per_idx=8 with opq)";
+    return -1;
+  }
   if (raw_.init(dim_)) return -1;
 
   if (params_.kind != IndexKind::FLAT) {

@@ -82,11 +82,13 @@ hipError_t argmin_rows(hipStream_t s, int64_t nrows, int ncols,
  * gamma_index_ivfpq.h:254-262):
  *   btab[ln][m][j] = 2 * (c_ln,m . cw_mj)        (train-time)
  *   atab[q][m][j]  = fmaf(-2, q_m . cw, ||cw||^2) (per search batch)
- * Sequential-fmaf arithmetic matching oracle_pct1_*_table. */
-hipError_t pq_tables_b(hipStream_t s, int d, int M, int nlist,
+ * Sequential-fmaf arithmetic matching oracle_pct1_*_table.
+ * ksub = 256 (nbits_per_idx=8) or 16 (nbits_per_idx=4) here and in every
+ * PQ entry point below; anything else is hipErrorInvalidValue. */
+hipError_t pq_tables_b(hipStream_t s, int d, int M, int ksub, int nlist,
                        const float *centroids, const float *codebooks,
                        float *btab);
-hipError_t pq_tables_a(hipStream_t s, int nq, int d, int M,
+hipError_t pq_tables_a(hipStream_t s, int nq, int d, int M, int ksub,
                        const float *queries, const float *codebooks,
                        float *atab);
 
@@ -98,12 +100,14 @@ hipError_t pq_tables_a(hipStream_t s, int nq, int d, int M,
  * scan: dis = coarse_dis + S_v + sum_m atab[q][m][code_m], which is
  * the same T = A + B sum grouped per vector — fp32-rounding-only
  * difference, same class as the documented pct1 deviation
- * (DESIGN.md "The L2 ADC table mode"). */
-hipError_t pq_sterm(hipStream_t s, int64_t n, int M, int nlist,
+ * (DESIGN.md "The L2 ADC table mode").
+ * codes are bucket-format entries: M bytes at ksub=256; at ksub=16 M/2
+ * bytes, byte b = sub-quantizer 2b in bits 0-3 and 2b+1 in bits 4-7. */
+hipError_t pq_sterm(hipStream_t s, int64_t n, int M, int ksub, int nlist,
                     const uint8_t *codes, const int32_t *asg,
                     int asg_const, const float *btab, float *out);
 /* Load-path batch: one launch rebuilds every bucket's S terms */
-hipError_t pq_sterm_buckets(hipStream_t s, int nlist, int M,
+hipError_t pq_sterm_buckets(hipStream_t s, int nlist, int M, int ksub,
                             const GammaBucketDev *bks, const float *btab);
 
 /* IVFPQ fused search: one workgroup per query; stages the query-level
@@ -120,7 +124,9 @@ hipError_t pq_sterm_buckets(hipStream_t s, int nlist, int M,
  * ~nq*nprobe/nlist times from DRAM). Results are identical: the
  * selector's top-k2 is order-independent and outputs are written at
  * the ORIGINAL query row. */
-hipError_t ivfpq_scan(hipStream_t s, int nq, int S, int d, int M,
+/* ksub=16 runs k_ivfpq_scan4 on packed 4-bit entries (M/2 bytes, low
+ * nibble = even sub-quantizer) with an M x 16 table; same contract. */
+hipError_t ivfpq_scan(hipStream_t s, int nq, int S, int d, int M, int ksub,
                       int nprobe,
                       int k2, const float *queries, const float *centroids,
                       const float *codebooks, const float *atab,
@@ -167,6 +173,12 @@ hipError_t residuals(hipStream_t s, int64_t n, int d, const float *x,
  * (pq.compute_codes, ivfpq.cc:494; ties -> lowest j). */
 hipError_t pq_encode(hipStream_t s, int64_t n, int d, int M, int ksub,
                      const float *x, const float *codebooks, uint8_t *codes);
+/* Same argmin at ksub=16, written as packed bucket entries: M/2 bytes
+ * per vector, byte b = code 2b in bits 0-3, code 2b+1 in bits 4-7. The
+ * training paths keep pq_encode's one-byte-per-code form. */
+hipError_t pq_encode_pack4(hipStream_t s, int64_t n, int d, int M,
+                           const float *x, const float *codebooks,
+                           uint8_t *codes);
 
 /* FLAT brute-force over the raw-vector segment table (no materialized
  * dist matrix): per query workgroup streams all n vectors. Used for small

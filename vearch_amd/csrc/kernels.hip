@@ -650,6 +650,233 @@ k_ivfpq_scan(int nq, int S, int d, int M, int nprobe, int k2,
     out_keys[((int64_t)q * S + sub) * k2 + i] = res[i];
 }
 
+/* ------------------------------------------- IVFPQ fused scan, 4-bit codes
+ * Same contract as k_ivfpq_scan for nbits_per_idx=4 (ksub=16). Entries
+ * are M/2 bytes: byte b holds sub-quantizer 2b in bits 0-3 and 2b+1 in
+ * bits 4-7, so a little-endian word decodes in ascending m by taking
+ * nibbles from bit 0 up. dis = dis0 (+ S_v) then += T[m][code_m] in
+ * ascending m, plain adds — bit-identical to the oracle at ksub=16.
+ * The table is M x 16 floats (2 KB at M=32): a row spans 16 consecutive
+ * LDS banks, so the per-m gather is conflict-free for any code pattern.
+ * MW = M/8 code words per entry (0 = generic runtime-M path, byte loads:
+ * entries such as M=12's 6 bytes are not word-aligned). Fast-path
+ * entries are 8, 16, 32 or 48 bytes in 256-B-aligned buckets, so they
+ * load as the widest vector that divides them. */
+template <int MW>
+__device__ __forceinline__ void gamma_load_code4(const uint8_t *p,
+                                                 uint32_t (&w)[MW]) {
+  if constexpr (MW % 4 == 0) {
+#pragma unroll
+    for (int i = 0; i < MW / 4; i++) {
+      uint4 v = ((const uint4 *)p)[i];
+      w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z;
+      w[4 * i + 3] = v.w;
+    }
+  } else if constexpr (MW % 2 == 0) {
+#pragma unroll
+    for (int i = 0; i < MW / 2; i++) {
+      uint2 v = ((const uint2 *)p)[i];
+      w[2 * i] = v.x; w[2 * i + 1] = v.y;
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < MW; i++) w[i] = ((const uint32_t *)p)[i];
+  }
+}
+
+template <bool IP, int MW, int BS, int CP>
+__global__ void __launch_bounds__(BS)
+k_ivfpq_scan4(int nq, int S, int d, int M, int nprobe, int k2,
+              const float *__restrict__ queries,
+              const float *__restrict__ centroids,
+              const float *__restrict__ codebooks,
+              const float *__restrict__ atab,
+              const float *__restrict__ probe_dists,
+              const GammaBucketDev *__restrict__ buckets, int nlist,
+              const int64_t *__restrict__ probes,
+              const uint32_t *__restrict__ bitmap,
+              uint64_t *__restrict__ out_keys,
+              const int *__restrict__ kill_flag,
+              const int32_t *__restrict__ qmap) {
+  extern __shared__ char smem[];
+  const int ksub = 16;
+  const int dsub = d / M;
+  const int csz = M >> 1;                           /* bytes per entry */
+  float *lut = (float *)smem;                       /* M*16 (M%4==0) */
+  uint64_t *sortbuf = (uint64_t *)(smem + (size_t)M * ksub * 4);
+  uint64_t *res = sortbuf + GAMMA_SORT_CAP;
+  float *qs = (float *)(res + k2);                  /* d (IP table build) */
+  float *dis0s = qs + d;                            /* 2 (one per half) */
+  long long *szsh = (long long *)(dis0s + 2);       /* 2 (list sizes) */
+  int *state = (int *)(szsh + 2) + 1;               /* int[2] */
+
+  const int bq = blockIdx.x / S;
+  const int sub = blockIdx.x - bq * S;
+  if (bq >= nq) return;
+  const int q = qmap ? qmap[bq] : bq;
+  const float *qg = queries + (int64_t)q * d;
+  for (int i = threadIdx.x; i < d; i += blockDim.x) qs[i] = qg[i];
+
+  GammaSelector sel;
+  sel.init(sortbuf, res, state, k2);  /* has the barrier qs needs */
+
+  if (IP) {
+    for (int e = threadIdx.x; e < M * ksub; e += blockDim.x) {
+      int m = e >> 4, j = e & 15;
+      const float *cw = codebooks + ((size_t)m * ksub + j) * dsub;
+      const float *qm = qs + m * dsub;
+      float acc = 0.0f;
+      for (int t = 0; t < dsub; t++) acc = fmaf(qm[t], cw[t], acc);
+      lut[e] = acc;
+    }
+    __syncthreads();
+  } else {
+    const float4 *Aq = (const float4 *)(atab + (size_t)q * M * ksub);
+    float4 *lut4 = (float4 *)lut;
+    for (int e = threadIdx.x; e < (M * ksub) >> 2; e += blockDim.x)
+      lut4[e] = Aq[e];
+    __syncthreads();
+  }
+
+  if (MW > 0) {
+    /* two probed lists in flight per workgroup, as in k_ivfpq_scan */
+    const int C = CP;
+    const int HB = BS / 2;
+    const int half = threadIdx.x >= HB ? 1 : 0;
+    const int tid = threadIdx.x - half * HB;
+    for (int t = 0;; t += 2) {
+      int p0 = sub + t * S;
+      if (p0 >= nprobe) break;
+      if (kill_flag &&
+          __hip_atomic_load(kill_flag, __ATOMIC_RELAXED,
+                            __HIP_MEMORY_SCOPE_AGENT))
+        break;
+      int p = sub + (t + half) * S;
+      int64_t ln = -1;
+      if (p < nprobe) ln = probes[(int64_t)q * nprobe + p];
+      if (ln >= nlist) ln = -1;
+      GammaBucketDev bk;
+      bk.size = 0;
+      if (ln >= 0) bk = buckets[ln];
+      float dis0 = 0.0f;
+      if (IP) {
+        if (tid == 0) { /* dis0 = dot(q, c), canonical order, per half */
+          float acc = 0.0f;
+          if (ln >= 0) {
+            const float *cent = centroids + (size_t)ln * d;
+            for (int e = 0; e < d; e++) acc = fmaf(qs[e], cent[e], acc);
+          }
+          dis0s[half] = acc;
+          szsh[half] = bk.size;
+        }
+      } else {
+        if (ln >= 0 && p < nprobe)
+          dis0 = probe_dists[(int64_t)q * nprobe + p];
+        if (tid == 0) szsh[half] = bk.size;
+      }
+      __syncthreads();
+      if (IP) dis0 = dis0s[half];
+      long long maxsz = szsh[0] > szsh[1] ? szsh[0] : szsh[1];
+      const uint32_t *ids = bk.ids;
+      const uint8_t *codes = (const uint8_t *)bk.data;
+      const float *svals = (const float *)bk.svals;
+      for (long long j0 = 0; j0 < maxsz; j0 += (long long)HB * C) {
+        long long jb = j0 + (long long)tid * C;
+        uint32_t w[C][MW ? MW : 1]; /* compile-time bounds -> registers */
+        int64_t idv[C];
+        float sv[C];
+#pragma unroll
+        for (int c = 0; c < C; c++) {
+          long long j = jb + c;
+          if (ln >= 0 && j < bk.size) {
+            idv[c] = (int64_t)(int32_t)ids[j]; /* bit31 -> negative */
+            if (!IP) sv[c] = svals[j];
+            gamma_load_code4<MW ? MW : 1>(codes + (size_t)j * (MW * 4),
+                                          w[c]);
+          } else {
+            idv[c] = -1; /* bit 63 set -> skipped below */
+            sv[c] = 0.0f;
+          }
+        }
+#pragma unroll
+        for (int c = 0; c < C; c++) {
+          int64_t id = idv[c];
+          if (!((uint64_t)id >> 63) &&
+              !gamma_bitmap_test(bitmap, (uint64_t)id)) {
+            float dis = IP ? dis0 : dis0 + sv[c];
+            const float *tab = lut;
+#pragma unroll
+            for (int mw = 0; mw < MW; mw++) {
+              uint32_t wv = w[c][mw];
+#pragma unroll
+              for (int nb = 0; nb < 8; nb++) {
+                dis += tab[(wv >> (4 * nb)) & 15u];
+                tab += ksub;
+              }
+            }
+            sel.push(gamma_make_key<IP>(dis, (uint32_t)id));
+          }
+        }
+        sel.maybe_flush(blockDim.x * C);
+      }
+      __syncthreads(); /* dis0s/szsh rewritten next pair */
+    }
+  } else {
+    for (int p = sub; p < nprobe; p += S) {
+      if (kill_flag &&
+          __hip_atomic_load(kill_flag, __ATOMIC_RELAXED,
+                            __HIP_MEMORY_SCOPE_AGENT))
+        break;
+      int64_t ln = probes[(int64_t)q * nprobe + p];
+      if (ln < 0 || ln >= nlist) continue;
+      GammaBucketDev bk = buckets[ln];
+      if (bk.size <= 0) continue;
+      const float *cent = centroids + (size_t)ln * d;
+
+      float dis0;
+      if (IP) {
+        if (threadIdx.x == 0) {  /* dis0 = dot(q, c), canonical order */
+          float acc = 0.0f;
+          for (int e = 0; e < d; e++) acc = fmaf(qs[e], cent[e], acc);
+          dis0s[0] = acc;
+        }
+        __syncthreads();
+        dis0 = dis0s[0];
+      } else {
+        dis0 = probe_dists[(int64_t)q * nprobe + p];
+      }
+
+      const uint32_t *ids = bk.ids;
+      const uint8_t *codes = (const uint8_t *)bk.data;
+      const float *svals = (const float *)bk.svals;
+      for (long long j0 = 0; j0 < bk.size; j0 += blockDim.x) {
+        long long j = j0 + threadIdx.x;
+        if (j < bk.size) {
+          int64_t id = (int64_t)(int32_t)ids[j];
+          if (!((uint64_t)id >> 63) &&
+              !gamma_bitmap_test(bitmap, (uint64_t)id)) {
+            /* byte loads: csz need not be a multiple of 4 */
+            const uint8_t *cb = codes + (size_t)j * csz;
+            float dis = IP ? dis0 : dis0 + svals[j];
+            const float *tab = lut;
+            for (int b = 0; b < csz; b++) {
+              uint32_t v = cb[b];
+              dis += tab[v & 15u]; tab += ksub;
+              dis += tab[v >> 4];  tab += ksub;
+            }
+            sel.push(gamma_make_key<IP>(dis, (uint32_t)id));
+          }
+        }
+        sel.maybe_flush(blockDim.x);
+      }
+      if (IP) __syncthreads(); /* dis0s rewritten next list */
+    }
+  }
+  sel.finish();
+  for (int i = threadIdx.x; i < k2; i += blockDim.x)
+    out_keys[((int64_t)q * S + sub) * k2 + i] = res[i];
+}
+
 __global__ void k_extract_probe0(int nq, int nprobe,
                                  const int64_t *__restrict__ probes,
                                  int32_t *__restrict__ out) {
@@ -665,7 +892,7 @@ hipError_t gk::extract_probe0(hipStream_t s, int nq, int nprobe,
 }
 
 hipError_t gk::ivfpq_scan(hipStream_t s, int nq, int S, int d, int M,
-                          int nprobe,
+                          int ksub, int nprobe,
                           int k2, const float *queries,
                           const float *centroids, const float *codebooks,
                           const float *atab,
@@ -674,7 +901,10 @@ hipError_t gk::ivfpq_scan(hipStream_t s, int nq, int S, int d, int M,
                           const int64_t *probes, const uint32_t *bitmap,
                           bool ip, uint64_t *out_keys,
                           const int *kill_flag, const int32_t *qmap) {
-  size_t smem = ((size_t)M * 256 * 4 + 7) / 8 * 8 +
+  if (ksub != 256 && ksub != 16) return hipErrorInvalidValue;
+  /* table M*ksub floats: 32 KB at M=32/8-bit, 2 KB at M=32/4-bit (small
+   * next to the 16 KB selector scratch) */
+  size_t smem = ((size_t)M * ksub * 4 + 7) / 8 * 8 +
                 (GAMMA_SORT_CAP + k2) * 8 + (d + 2) * 4 +
                 2 * sizeof(long long) + 4 * sizeof(int);
   if (smem > 160 * 1024) return hipErrorInvalidValue;
@@ -703,19 +933,42 @@ hipError_t gk::ivfpq_scan(hipStream_t s, int nq, int S, int d, int M,
               (M == 16 || M == 32 || M == 64 || M == 96);
   if (!((k2 + BS * CSEL) <= GAMMA_SORT_CAP)) CSEL = 1;
   dim3 g((uint32_t)nq * (uint32_t)S);
-#define GAMMA_LAUNCH_SCAN(IPV, MWV, BSV, CPV)                             \
-  k_ivfpq_scan<IPV, MWV, BSV, CPV><<<g, dim3(BSV), smem, s>>>(            \
+#define GAMMA_LAUNCH_SCAN_K(KERN, IPV, MWV, BSV, CPV)                     \
+  KERN<IPV, MWV, BSV, CPV><<<g, dim3(BSV), smem, s>>>(                    \
       nq, S, d, M, nprobe, k2, queries, centroids, codebooks, atab,       \
       probe_dists, buckets, nlist, probes, bitmap, out_keys,              \
       kill_flag, qmap)
-#define GAMMA_LAUNCH_SCAN_BS(IPV, MWV)                                    \
+#define GAMMA_LAUNCH_SCAN_K_BS(KERN, IPV, MWV)                            \
   do {                                                                    \
-    if (BS == 256 && CSEL == 2) GAMMA_LAUNCH_SCAN(IPV, MWV, 256, 2);      \
-    else if (BS == 256) GAMMA_LAUNCH_SCAN(IPV, MWV, 256, 1);              \
-    else if (CSEL == 2) GAMMA_LAUNCH_SCAN(IPV, MWV, 512, 2);              \
-    else GAMMA_LAUNCH_SCAN(IPV, MWV, 512, 1);                             \
+    if (BS == 256 && CSEL == 2)                                           \
+      GAMMA_LAUNCH_SCAN_K(KERN, IPV, MWV, 256, 2);                        \
+    else if (BS == 256) GAMMA_LAUNCH_SCAN_K(KERN, IPV, MWV, 256, 1);      \
+    else if (CSEL == 2) GAMMA_LAUNCH_SCAN_K(KERN, IPV, MWV, 512, 2);      \
+    else GAMMA_LAUNCH_SCAN_K(KERN, IPV, MWV, 512, 1);                     \
   } while (0)
-  if (ip) {
+#define GAMMA_LAUNCH_SCAN(IPV, MWV, BSV, CPV)                             \
+  GAMMA_LAUNCH_SCAN_K(k_ivfpq_scan, IPV, MWV, BSV, CPV)
+#define GAMMA_LAUNCH_SCAN_BS(IPV, MWV)                                    \
+  GAMMA_LAUNCH_SCAN_K_BS(k_ivfpq_scan, IPV, MWV)
+#define GAMMA_LAUNCH_SCAN4(IPV, MWV, BSV, CPV)                            \
+  GAMMA_LAUNCH_SCAN_K(k_ivfpq_scan4, IPV, MWV, BSV, CPV)
+#define GAMMA_LAUNCH_SCAN4_BS(IPV, MWV)                                   \
+  GAMMA_LAUNCH_SCAN_K_BS(k_ivfpq_scan4, IPV, MWV)
+  if (ksub == 16) { /* 4-bit codes: MW = M/8 words per entry */
+    if (ip) {
+      if (!fast) GAMMA_LAUNCH_SCAN4(true, 0, WG, 1);
+      else if (M == 16) GAMMA_LAUNCH_SCAN4_BS(true, 2);
+      else if (M == 32) GAMMA_LAUNCH_SCAN4_BS(true, 4);
+      else if (M == 64) GAMMA_LAUNCH_SCAN4_BS(true, 8);
+      else GAMMA_LAUNCH_SCAN4_BS(true, 12);
+    } else {
+      if (!fast) GAMMA_LAUNCH_SCAN4(false, 0, WG, 1);
+      else if (M == 16) GAMMA_LAUNCH_SCAN4_BS(false, 2);
+      else if (M == 32) GAMMA_LAUNCH_SCAN4_BS(false, 4);
+      else if (M == 64) GAMMA_LAUNCH_SCAN4_BS(false, 8);
+      else GAMMA_LAUNCH_SCAN4_BS(false, 12);
+    }
+  } else if (ip) {
     if (!fast) GAMMA_LAUNCH_SCAN(true, 0, WG, 1);
     else if (M == 16) GAMMA_LAUNCH_SCAN_BS(true, 4);
     else if (M == 32) GAMMA_LAUNCH_SCAN_BS(true, 8);
@@ -728,8 +981,12 @@ hipError_t gk::ivfpq_scan(hipStream_t s, int nq, int S, int d, int M,
     else if (M == 64) GAMMA_LAUNCH_SCAN_BS(false, 16);
     else GAMMA_LAUNCH_SCAN_BS(false, 24);
   }
+#undef GAMMA_LAUNCH_SCAN4_BS
+#undef GAMMA_LAUNCH_SCAN4
 #undef GAMMA_LAUNCH_SCAN_BS
 #undef GAMMA_LAUNCH_SCAN
+#undef GAMMA_LAUNCH_SCAN_K_BS
+#undef GAMMA_LAUNCH_SCAN_K
   return hipGetLastError();
 }
 
@@ -1147,20 +1404,24 @@ hipError_t gk::unpack_keys(hipStream_t s, int64_t n, const uint64_t *keys,
   return hipGetLastError();
 }
 
-/* ---------------------------------------------------- pct1 ADC tables */
+/* ---------------------------------------------------- pct1 ADC tables
+ * KB = log2(ksub): 8 (nbits_per_idx=8) or 4 (nbits_per_idx=4). The
+ * arithmetic does not depend on KB, only the table indexing does. */
+template <int KB>
 __global__ void k_pq_btable(int d, int M, int nlist,
                             const float *__restrict__ centroids,
                             const float *__restrict__ codebooks,
                             float *__restrict__ btab) {
+  const int KSUB = 1 << KB;
   int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t total = (int64_t)nlist * M * 256;
+  int64_t total = (int64_t)nlist * M * KSUB;
   if (e >= total) return;
   int dsub = d / M;
-  int j = (int)(e & 255);
-  int m = (int)((e >> 8) % M);
-  int64_t ln = e / ((int64_t)M * 256);
+  int j = (int)(e & (KSUB - 1));
+  int m = (int)((e >> KB) % M);
+  int64_t ln = e / ((int64_t)M * KSUB);
   const float *cm = centroids + ln * d + m * dsub;
-  const float *cw = codebooks + ((size_t)m * 256 + j) * dsub;
+  const float *cw = codebooks + ((size_t)m * KSUB + j) * dsub;
   float dot = 0.0f;
   if ((dsub & 3) == 0) {
 #pragma unroll 2
@@ -1178,28 +1439,36 @@ __global__ void k_pq_btable(int d, int M, int nlist,
   btab[e] = 2.0f * dot;
 }
 
-hipError_t gk::pq_tables_b(hipStream_t s, int d, int M, int nlist,
+hipError_t gk::pq_tables_b(hipStream_t s, int d, int M, int ksub, int nlist,
                            const float *centroids, const float *codebooks,
                            float *btab) {
-  int64_t total = (int64_t)nlist * M * 256;
-  k_pq_btable<<<dim3((uint32_t)((total + WG - 1) / WG)), dim3(WG), 0, s>>>(
-      d, M, nlist, centroids, codebooks, btab);
+  if (ksub != 256 && ksub != 16) return hipErrorInvalidValue;
+  int64_t total = (int64_t)nlist * M * ksub;
+  dim3 g((uint32_t)((total + WG - 1) / WG));
+  if (ksub == 256)
+    k_pq_btable<8><<<g, dim3(WG), 0, s>>>(d, M, nlist, centroids, codebooks,
+                                          btab);
+  else
+    k_pq_btable<4><<<g, dim3(WG), 0, s>>>(d, M, nlist, centroids, codebooks,
+                                          btab);
   return hipGetLastError();
 }
 
+template <int KB>
 __global__ void k_pq_atable(int nq, int d, int M,
                             const float *__restrict__ queries,
                             const float *__restrict__ codebooks,
                             float *__restrict__ atab) {
+  const int KSUB = 1 << KB;
   int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t total = (int64_t)nq * M * 256;
+  int64_t total = (int64_t)nq * M * KSUB;
   if (e >= total) return;
   int dsub = d / M;
-  int j = (int)(e & 255);
-  int m = (int)((e >> 8) % M);
-  int64_t q = e / ((int64_t)M * 256);
+  int j = (int)(e & (KSUB - 1));
+  int m = (int)((e >> KB) % M);
+  int64_t q = e / ((int64_t)M * KSUB);
   const float *qm = queries + q * d + m * dsub;
-  const float *cw = codebooks + ((size_t)m * 256 + j) * dsub;
+  const float *cw = codebooks + ((size_t)m * KSUB + j) * dsub;
   float cwn = 0.0f, dot = 0.0f;
   if ((dsub & 3) == 0) { /* float4 loads, same fmaf order */
 #pragma unroll 2
@@ -1222,18 +1491,44 @@ __global__ void k_pq_atable(int nq, int d, int M,
   atab[e] = fmaf(-2.0f, dot, cwn);
 }
 
-hipError_t gk::pq_tables_a(hipStream_t s, int nq, int d, int M,
+hipError_t gk::pq_tables_a(hipStream_t s, int nq, int d, int M, int ksub,
                            const float *queries, const float *codebooks,
                            float *atab) {
-  int64_t total = (int64_t)nq * M * 256;
-  k_pq_atable<<<dim3((uint32_t)((total + WG - 1) / WG)), dim3(WG), 0, s>>>(
-      nq, d, M, queries, codebooks, atab);
+  if (ksub != 256 && ksub != 16) return hipErrorInvalidValue;
+  int64_t total = (int64_t)nq * M * ksub;
+  dim3 g((uint32_t)((total + WG - 1) / WG));
+  if (ksub == 256)
+    k_pq_atable<8><<<g, dim3(WG), 0, s>>>(nq, d, M, queries, codebooks,
+                                          atab);
+  else
+    k_pq_atable<4><<<g, dim3(WG), 0, s>>>(nq, d, M, queries, codebooks,
+                                          atab);
   return hipGetLastError();
+}
+
+/* S = sum_m B[m][code_m], plain adds in ascending m. KB=8: one byte per
+ * sub-quantizer. KB=4: packed entries of M/2 bytes, byte b = sub-quantizer
+ * 2b in bits 0-3 and 2b+1 in bits 4-7 (low nibble first). */
+template <int KB>
+__device__ __forceinline__ float gamma_sterm_sum(const float *B,
+                                                 const uint8_t *c, int M) {
+  float acc = 0.0f;
+  if (KB == 8) {
+    for (int m = 0; m < M; m++) acc += B[(size_t)m * 256 + c[m]];
+  } else {
+    for (int b = 0; b < (M >> 1); b++) {
+      uint32_t v = c[b];
+      acc += B[(size_t)(2 * b) * 16 + (v & 15u)];
+      acc += B[(size_t)(2 * b + 1) * 16 + (v >> 4)];
+    }
+  }
+  return acc;
 }
 
 /* per-vector S term: out[i] = sum_m btab[asg_i][m][code_i[m]], plain
  * adds in m order (the oracle mirrors this exactly —
  * oracle_ivfpq_search_pct1's per-code B sum) */
+template <int KB>
 __global__ void k_pq_sterm(int64_t n, int M, int nlist,
                            const uint8_t *__restrict__ codes,
                            const int32_t *__restrict__ asg, int asg_const,
@@ -1248,47 +1543,53 @@ __global__ void k_pq_sterm(int64_t n, int M, int nlist,
     out[i] = 0.0f;
     return;
   }
-  const float *B = btab + (size_t)ln * M * 256;
-  const uint8_t *c = codes + (size_t)i * M;
-  float acc = 0.0f;
-  for (int m = 0; m < M; m++) acc += B[(size_t)m * 256 + c[m]];
-  out[i] = acc;
+  const float *B = btab + ((size_t)ln * M << KB);
+  const uint8_t *c = codes + (size_t)i * (M * KB / 8);
+  out[i] = gamma_sterm_sum<KB>(B, c, M);
 }
 
 /* Load-path batch: rebuild every bucket's S terms in one launch
  * (block per bucket) instead of one k_pq_sterm launch per bucket —
  * 16384 launches / 0.27 s of Load time at the headline nlist. */
+template <int KB>
 __global__ void k_pq_sterm_buckets(int nlist, int M,
                                    const GammaBucketDev *__restrict__ bks,
                                    const float *__restrict__ btab) {
   const GammaBucketDev bk = bks[blockIdx.x];
   if (!bk.svals || bk.size <= 0) return;
-  const float *B = btab + (size_t)blockIdx.x * M * 256;
+  const float *B = btab + ((size_t)blockIdx.x * M << KB);
   const uint8_t *codes = (const uint8_t *)bk.data;
   float *sv = (float *)bk.svals; /* writable: Load owns the buckets */
-  for (long long j = threadIdx.x; j < bk.size; j += blockDim.x) {
-    const uint8_t *c = codes + (size_t)j * M;
-    float acc = 0.0f;
-    for (int m = 0; m < M; m++) acc += B[(size_t)m * 256 + c[m]];
-    sv[j] = acc;
-  }
+  for (long long j = threadIdx.x; j < bk.size; j += blockDim.x)
+    sv[j] = gamma_sterm_sum<KB>(B, codes + (size_t)j * (M * KB / 8), M);
 }
 
-hipError_t gk::pq_sterm_buckets(hipStream_t s, int nlist, int M,
+hipError_t gk::pq_sterm_buckets(hipStream_t s, int nlist, int M, int ksub,
                                 const GammaBucketDev *bks,
                                 const float *btab) {
+  if (ksub != 256 && ksub != 16) return hipErrorInvalidValue;
   if (nlist <= 0) return hipSuccess;
-  k_pq_sterm_buckets<<<dim3((uint32_t)nlist), dim3(256), 0, s>>>(
-      nlist, M, bks, btab);
+  if (ksub == 256)
+    k_pq_sterm_buckets<8><<<dim3((uint32_t)nlist), dim3(256), 0, s>>>(
+        nlist, M, bks, btab);
+  else
+    k_pq_sterm_buckets<4><<<dim3((uint32_t)nlist), dim3(256), 0, s>>>(
+        nlist, M, bks, btab);
   return hipGetLastError();
 }
 
-hipError_t gk::pq_sterm(hipStream_t s, int64_t n, int M, int nlist,
+hipError_t gk::pq_sterm(hipStream_t s, int64_t n, int M, int ksub, int nlist,
                         const uint8_t *codes, const int32_t *asg,
                         int asg_const, const float *btab, float *out) {
+  if (ksub != 256 && ksub != 16) return hipErrorInvalidValue;
   if (n <= 0) return hipSuccess;
-  k_pq_sterm<<<dim3((uint32_t)((n + WG - 1) / WG)), dim3(WG), 0, s>>>(
-      n, M, nlist, codes, asg, asg_const, btab, out);
+  dim3 g((uint32_t)((n + WG - 1) / WG));
+  if (ksub == 256)
+    k_pq_sterm<8><<<g, dim3(WG), 0, s>>>(n, M, nlist, codes, asg, asg_const,
+                                         btab, out);
+  else
+    k_pq_sterm<4><<<g, dim3(WG), 0, s>>>(n, M, nlist, codes, asg, asg_const,
+                                         btab, out);
   return hipGetLastError();
 }
 
@@ -1353,17 +1654,10 @@ hipError_t gk::residuals(hipStream_t s, int64_t n, int d, const float *x,
 }
 
 /* ----------------------------------------------------------- PQ encode */
-__global__ void k_pq_encode(int64_t n, int d, int M, int ksub,
-                            const float *__restrict__ x,
-                            const float *__restrict__ codebooks,
-                            uint8_t *__restrict__ codes) {
-  int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= n * M) return;
-  int64_t i = idx / M;
-  int m = (int)(idx - i * M);
-  int dsub = d / M;
-  const float *xm = x + i * d + m * dsub;
-  const float *cb = codebooks + (size_t)m * ksub * dsub;
+/* argmin_j ||xm - cb[j]||^2, sequential fmaf, ties -> lowest j */
+__device__ __forceinline__ int gamma_pq_argmin(const float *xm,
+                                               const float *cb, int ksub,
+                                               int dsub) {
   float best = INFINITY;
   int bestj = 0;
   for (int j = 0; j < ksub; j++) {
@@ -1375,7 +1669,20 @@ __global__ void k_pq_encode(int64_t n, int d, int M, int ksub,
     }
     if (acc < best) { best = acc; bestj = j; }
   }
-  codes[idx] = (uint8_t)bestj;
+  return bestj;
+}
+
+__global__ void k_pq_encode(int64_t n, int d, int M, int ksub,
+                            const float *__restrict__ x,
+                            const float *__restrict__ codebooks,
+                            uint8_t *__restrict__ codes) {
+  int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n * M) return;
+  int64_t i = idx / M;
+  int m = (int)(idx - i * M);
+  int dsub = d / M;
+  codes[idx] = (uint8_t)gamma_pq_argmin(
+      x + i * d + m * dsub, codebooks + (size_t)m * ksub * dsub, ksub, dsub);
 }
 
 hipError_t gk::pq_encode(hipStream_t s, int64_t n, int d, int M, int ksub,
@@ -1385,5 +1692,35 @@ hipError_t gk::pq_encode(hipStream_t s, int64_t n, int d, int M, int ksub,
   int64_t blocks = (n * M + WG - 1) / WG;
   k_pq_encode<<<dim3((uint32_t)blocks), dim3(WG), 0, s>>>(n, d, M, ksub, x,
                                                           codebooks, codes);
+  return hipGetLastError();
+}
+
+/* 4-bit ingest encode: one thread per output byte = two sub-quantizers
+ * (2b in bits 0-3, 2b+1 in bits 4-7), same argmin as k_pq_encode */
+__global__ void k_pq_encode_pack4(int64_t n, int d, int M,
+                                  const float *__restrict__ x,
+                                  const float *__restrict__ codebooks,
+                                  uint8_t *__restrict__ codes) {
+  const int nb = M >> 1;
+  int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n * nb) return;
+  int64_t i = idx / nb;
+  int m = (int)(idx - i * nb) * 2;
+  int dsub = d / M;
+  const float *xm = x + i * d + m * dsub;
+  const float *cb = codebooks + (size_t)m * 16 * dsub;
+  int lo = gamma_pq_argmin(xm, cb, 16, dsub);
+  int hi = gamma_pq_argmin(xm + dsub, cb + (size_t)16 * dsub, 16, dsub);
+  codes[idx] = (uint8_t)(lo | (hi << 4));
+}
+
+hipError_t gk::pq_encode_pack4(hipStream_t s, int64_t n, int d, int M,
+                               const float *x, const float *codebooks,
+                               uint8_t *codes) {
+  if (M & 1) return hipErrorInvalidValue;
+  if (n == 0) return hipSuccess;
+  int64_t blocks = (n * (M >> 1) + WG - 1) / WG;
+  k_pq_encode_pack4<<<dim3((uint32_t)blocks), dim3(WG), 0, s>>>(
+      n, d, M, x, codebooks, codes);
   return hipGetLastError();
 }
