@@ -82,6 +82,46 @@ int64_t GammaDebugNumDocs(void *engine);
  * [3]=rerank+merge, [4]=D2H, [5]=total wall. Returns 0. */
 int GammaLastSearchTiming(void *engine, double *us6);
 
+/* ---- kernel test hooks (vearch_amd/csrc/ktest.cpp) ----
+ * One entry per gk:: host function of csrc/kernels.h, same arguments
+ * minus the stream, bool -> int. EVERY pointer is a DEVICE pointer. Each
+ * hook launches on the null stream, synchronises the device and returns
+ * the first non-zero hipError_t (0 = ok). Test-only: nothing on the
+ * product path calls them. See kernels.h for each kernel's contract
+ * (d % 4 == 0, k2 <= 1024, select_rows_full ncols <= 8192, sort_rows
+ * ncand <= 2048, ksub in {16, 256}). */
+int GammaKTestDotsMfma(const float *Q, int nq, const float *B, int64_t n,
+                       int d, float *out);
+int GammaKTestSelectFromDots(int nq, int64_t ncols, int64_t col_base,
+                             int64_t ld, const float *dots,
+                             const float *qnorms, const float *bnorms,
+                             int l2, int ip_order, const uint32_t *bitmap,
+                             int k2, uint64_t *state_keys, int seeded);
+int GammaKTestSelectRowsFull(int nq, int ncols, int64_t ld,
+                             const float *dots, const float *qnorms,
+                             const float *bnorms, int l2, int ip_order,
+                             int k2, float *out_dists, int64_t *out_ids);
+int GammaKTestArgminRows(int64_t nrows, int ncols, const float *dots,
+                         const float *qnorms, const float *bnorms, int l2,
+                         int32_t *out);
+/* segs: device array of n_segs device pointers (segment s holds vectors
+ * [s << seg_shift, (s + 1) << seg_shift)) */
+int GammaKTestRerank(int nq, int ncand, int d, const float *queries,
+                     const float *const *segs, int n_segs, int seg_shift,
+                     int ip, const uint64_t *keys_in, uint64_t *keys_out);
+int GammaKTestSortRows(int nq, int ncand, int k, const uint64_t *keys, int ip,
+                       float *out_dists, int64_t *out_ids);
+int GammaKTestUnpackKeys(int64_t n, const uint64_t *keys, int ip,
+                         float *out_dists, int64_t *out_ids);
+int GammaKTestPqEncode(int64_t n, int d, int M, int ksub, const float *x,
+                       const float *codebooks, uint8_t *codes);
+int GammaKTestPqEncodePack4(int64_t n, int d, int M, const float *x,
+                            const float *codebooks, uint8_t *codes);
+int GammaKTestFlatStreamScan(int nq, int64_t n, int d, int k2,
+                             const float *queries, const float *const *segs,
+                             int seg_shift, const uint32_t *bitmap, int ip,
+                             uint64_t *out_keys);
+
 #ifdef __cplusplus
 }
 #endif

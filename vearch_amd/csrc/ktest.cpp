@@ -1,0 +1,90 @@
+/*
+ * ktest.cpp — kernel test hooks (include/gamma_bench.h): one plain C
+ * entry per gk:: host function so the test suite can drive a single
+ * kernel on tiny device arrays. Every pointer is a DEVICE pointer. Each
+ * hook launches on the null stream, synchronises the device and returns
+ * the first non-zero hipError_t (0 = ok). No logic beyond that lives
+ * here; the product path never calls these.
+ */
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/gamma_bench.h"
+#include "kernels.h"
+
+static int kt_done(hipError_t launch) {
+  hipError_t sync = hipDeviceSynchronize();
+  return (int)(launch != hipSuccess ? launch : sync);
+}
+
+extern "C" {
+
+int GammaKTestDotsMfma(const float *Q, int nq, const float *B, int64_t n,
+                       int d, float *out) {
+  return kt_done(gk::dots_mfma(nullptr, Q, nq, B, n, d, out));
+}
+
+int GammaKTestSelectFromDots(int nq, int64_t ncols, int64_t col_base,
+                             int64_t ld, const float *dots,
+                             const float *qnorms, const float *bnorms,
+                             int l2, int ip_order, const uint32_t *bitmap,
+                             int k2, uint64_t *state_keys, int seeded) {
+  return kt_done(gk::select_from_dots(nullptr, nq, ncols, col_base, ld, dots,
+                                      qnorms, bnorms, l2 != 0, ip_order != 0,
+                                      bitmap, k2, state_keys, seeded != 0));
+}
+
+int GammaKTestSelectRowsFull(int nq, int ncols, int64_t ld,
+                             const float *dots, const float *qnorms,
+                             const float *bnorms, int l2, int ip_order,
+                             int k2, float *out_dists, int64_t *out_ids) {
+  return kt_done(gk::select_rows_full(nullptr, nq, ncols, ld, dots, qnorms,
+                                      bnorms, l2 != 0, ip_order != 0, k2,
+                                      out_dists, out_ids));
+}
+
+int GammaKTestArgminRows(int64_t nrows, int ncols, const float *dots,
+                         const float *qnorms, const float *bnorms, int l2,
+                         int32_t *out) {
+  return kt_done(gk::argmin_rows(nullptr, nrows, ncols, dots, qnorms, bnorms,
+                                 l2 != 0, out));
+}
+
+int GammaKTestRerank(int nq, int ncand, int d, const float *queries,
+                     const float *const *segs, int n_segs, int seg_shift,
+                     int ip, const uint64_t *keys_in, uint64_t *keys_out) {
+  return kt_done(gk::rerank(nullptr, nq, ncand, d, queries, segs, n_segs,
+                            seg_shift, ip != 0, keys_in, keys_out));
+}
+
+int GammaKTestSortRows(int nq, int ncand, int k, const uint64_t *keys, int ip,
+                       float *out_dists, int64_t *out_ids) {
+  return kt_done(gk::sort_rows(nullptr, nq, ncand, k, keys, ip != 0,
+                               out_dists, out_ids));
+}
+
+int GammaKTestUnpackKeys(int64_t n, const uint64_t *keys, int ip,
+                         float *out_dists, int64_t *out_ids) {
+  return kt_done(gk::unpack_keys(nullptr, n, keys, ip != 0, out_dists,
+                                 out_ids));
+}
+
+int GammaKTestPqEncode(int64_t n, int d, int M, int ksub, const float *x,
+                       const float *codebooks, uint8_t *codes) {
+  return kt_done(gk::pq_encode(nullptr, n, d, M, ksub, x, codebooks, codes));
+}
+
+int GammaKTestPqEncodePack4(int64_t n, int d, int M, const float *x,
+                            const float *codebooks, uint8_t *codes) {
+  return kt_done(gk::pq_encode_pack4(nullptr, n, d, M, x, codebooks, codes));
+}
+
+int GammaKTestFlatStreamScan(int nq, int64_t n, int d, int k2,
+                             const float *queries, const float *const *segs,
+                             int seg_shift, const uint32_t *bitmap, int ip,
+                             uint64_t *out_keys) {
+  return kt_done(gk::flat_stream_scan(nullptr, nq, n, d, k2, queries, segs,
+                                      seg_shift, bitmap, ip != 0, out_keys));
+}
+
+} /* extern "C" */

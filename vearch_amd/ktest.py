@@ -1,0 +1,245 @@
+"""ctypes wrapper over the kernel test hooks of libgamma.so
+(include/gamma_bench.h "kernel test hooks", csrc/ktest.cpp): each function
+drives ONE gk:: kernel entry on torch device tensors. TEST ONLY — the
+product path never imports this module.
+
+u64 keys travel as torch.int64 tensors (same bits); `keys_to_dev` /
+`keys_to_np` convert from/to numpy uint64."""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import engine
+
+_ready = False
+
+
+class KTestError(RuntimeError):
+    """A hook returned a non-zero hipError_t (`.code`)."""
+
+    def __init__(self, name, code):
+        super().__init__(f"{name} failed: hipError_t {code}")
+        self.code = code
+
+
+def _lib():
+    global _ready
+    L = engine.lib()
+    if not _ready:
+        c = ctypes
+        vp, i32, i64 = c.c_void_p, c.c_int, c.c_int64
+        L.GammaKTestDotsMfma.argtypes = [vp, i32, vp, i64, i32, vp]
+        L.GammaKTestSelectFromDots.argtypes = [
+            i32, i64, i64, i64, vp, vp, vp, i32, i32, vp, i32, vp, i32]
+        L.GammaKTestSelectRowsFull.argtypes = [
+            i32, i32, i64, vp, vp, vp, i32, i32, i32, vp, vp]
+        L.GammaKTestArgminRows.argtypes = [i64, i32, vp, vp, vp, i32, vp]
+        L.GammaKTestRerank.argtypes = [
+            i32, i32, i32, vp, vp, i32, i32, i32, vp, vp]
+        L.GammaKTestSortRows.argtypes = [i32, i32, i32, vp, i32, vp, vp]
+        L.GammaKTestUnpackKeys.argtypes = [i64, vp, i32, vp, vp]
+        L.GammaKTestPqEncode.argtypes = [i64, i32, i32, i32, vp, vp, vp]
+        L.GammaKTestPqEncodePack4.argtypes = [i64, i32, i32, vp, vp, vp]
+        L.GammaKTestFlatStreamScan.argtypes = [
+            i32, i64, i32, i32, vp, vp, i32, vp, i32, vp]
+        _ready = True
+    return L
+
+
+def _p(t, dtype=None):
+    """device pointer of a tensor (None -> NULL)"""
+    if t is None:
+        return None
+    assert t.is_cuda, "kernel hooks take device tensors only"
+    if dtype is not None:
+        assert t.dtype == dtype, f"expected {dtype}, got {t.dtype}"
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def _call(name, *args):
+    torch.cuda.synchronize()  # inputs were produced on torch's stream
+    rc = getattr(_lib(), name)(*args)
+    if rc != 0:
+        raise KTestError(name, rc)
+
+
+def keys_to_dev(keys_u64):
+    """numpy uint64 keys -> device int64 tensor with the same bits"""
+    a = np.ascontiguousarray(keys_u64, dtype=np.uint64)
+    return torch.from_numpy(a.view(np.int64).copy()).cuda()
+
+
+def keys_to_np(keys_dev):
+    """device int64 key tensor -> numpy uint64"""
+    return keys_dev.cpu().numpy().view(np.uint64)
+
+
+def bitmap_to_dev(words_u32):
+    a = np.ascontiguousarray(words_u32, dtype=np.uint32)
+    return torch.from_numpy(a.view(np.int32).copy()).cuda()
+
+
+def seg_table(segs):
+    """device array of device pointers, one per segment tensor. The
+    caller keeps `segs` alive while the table is in use."""
+    for t in segs:
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+    return torch.tensor([t.data_ptr() for t in segs],
+                        dtype=torch.int64).cuda()
+
+
+def split_segments(base_np, seg_shift):
+    """(n, d) host array -> list of separately allocated device segments
+    of 1 << seg_shift rows (the last one may be short)."""
+    step = 1 << seg_shift
+    base_np = np.ascontiguousarray(base_np, dtype=np.float32)
+    return [torch.from_numpy(base_np[i:i + step].copy()).cuda()
+            for i in range(0, base_np.shape[0], step)]
+
+
+# ------------------------------------------------------------------ hooks
+def dots_mfma(Q, B):
+    """out[i][j] = dot(Q_i, B_j); Q (nq, d), B (n, d) f32 contiguous."""
+    assert Q.is_contiguous() and B.is_contiguous()
+    nq, d = Q.shape
+    n = B.shape[0]
+    assert B.shape[1] == d and d % 4 == 0
+    out = torch.full((nq, n), float("nan"), dtype=torch.float32,
+                     device=Q.device)
+    _call("GammaKTestDotsMfma", _p(Q, torch.float32), nq,
+          _p(B, torch.float32), n, d, _p(out))
+    return out
+
+
+def select_from_dots(dots, ncols, k2, l2, ip_order, qnorms=None,
+                     bnorms=None, col_base=0, bitmap=None, state=None,
+                     seeded=False):
+    """dots: (nq, ld) device tensor whose first `ncols` columns are
+    selected on (ld = row stride). bnorms and bitmap are indexed by the
+    global id col_base + c. Returns the (nq, k2) key state (int64 bits);
+    pass it back as `state` with seeded=True to accumulate."""
+    assert dots.dim() == 2 and dots.stride(1) == 1
+    nq, ld = dots.shape[0], dots.stride(0)
+    assert 0 < ncols <= dots.shape[1] and 1 <= k2 <= 1024
+    if l2:
+        assert qnorms is not None and bnorms is not None
+        assert qnorms.numel() >= nq and bnorms.numel() >= col_base + ncols
+    if state is None:
+        assert not seeded
+        state = torch.full((nq, k2), 0x5A5A5A5A5A5A5A5A, dtype=torch.int64,
+                           device=dots.device)
+    assert state.shape == (nq, k2) and state.is_contiguous()
+    _call("GammaKTestSelectFromDots", nq, ncols, col_base, ld,
+          _p(dots, torch.float32), _p(qnorms, torch.float32),
+          _p(bnorms, torch.float32), int(bool(l2)), int(bool(ip_order)),
+          _p(bitmap, torch.int32), k2, _p(state, torch.int64),
+          int(bool(seeded)))
+    return state
+
+
+def select_rows_full(dots, ncols, k2, l2, ip_order, qnorms=None,
+                     bnorms=None):
+    """Full-sort row select; returns (dists f32, ids int64), (nq, k2).
+    Outputs are pre-filled with a sentinel (-7) so a refused launch is
+    visible."""
+    assert dots.dim() == 2 and dots.stride(1) == 1
+    nq, ld = dots.shape[0], dots.stride(0)
+    assert 0 < ncols <= dots.shape[1]
+    od = torch.full((nq, k2), -7.0, dtype=torch.float32, device=dots.device)
+    oi = torch.full((nq, k2), -7, dtype=torch.int64, device=dots.device)
+    _call("GammaKTestSelectRowsFull", nq, ncols, ld,
+          _p(dots, torch.float32), _p(qnorms, torch.float32),
+          _p(bnorms, torch.float32), int(bool(l2)), int(bool(ip_order)),
+          k2, _p(od), _p(oi))
+    return od, oi
+
+
+def argmin_rows(dots, l2, qnorms=None, bnorms=None):
+    """argmin per row of a contiguous (nrows, ncols) matrix -> int32."""
+    assert dots.dim() == 2 and dots.is_contiguous()
+    nrows, ncols = dots.shape
+    out = torch.full((nrows,), -7, dtype=torch.int32, device=dots.device)
+    _call("GammaKTestArgminRows", nrows, ncols, _p(dots, torch.float32),
+          _p(qnorms, torch.float32), _p(bnorms, torch.float32),
+          int(bool(l2)), _p(out))
+    return out
+
+
+def rerank(queries, segs, seg_shift, ip, keys_in, keys_out=None):
+    """Canonical re-rank of keys_in (nq, ncand) through the segment list
+    `segs` (device tensors of 1 << seg_shift rows). keys_out may be
+    keys_in itself (in-place)."""
+    assert queries.is_contiguous() and keys_in.is_contiguous()
+    nq, d = queries.shape
+    ncand = keys_in.shape[1]
+    assert keys_in.shape[0] == nq and d % 4 == 0
+    table = seg_table(segs)
+    if keys_out is None:
+        keys_out = torch.full_like(keys_in, 0x5A5A5A5A5A5A5A5A)
+    _call("GammaKTestRerank", nq, ncand, d, _p(queries, torch.float32),
+          _p(table), len(segs), seg_shift, int(bool(ip)),
+          _p(keys_in, torch.int64), _p(keys_out, torch.int64))
+    return keys_out
+
+
+def sort_rows(keys, k, ip):
+    """Per-row sort of (nq, ncand) keys -> top-k (dists, ids)."""
+    assert keys.dim() == 2 and keys.is_contiguous()
+    nq, ncand = keys.shape
+    assert ncand <= 2048
+    od = torch.full((nq, k), -7.0, dtype=torch.float32, device=keys.device)
+    oi = torch.full((nq, k), -7, dtype=torch.int64, device=keys.device)
+    _call("GammaKTestSortRows", nq, ncand, k, _p(keys, torch.int64),
+          int(bool(ip)), _p(od), _p(oi))
+    return od, oi
+
+
+def unpack_keys(keys, ip):
+    """keys (any shape, contiguous) -> (dists, ids) of the same shape."""
+    assert keys.is_contiguous()
+    od = torch.full(keys.shape, -7.0, dtype=torch.float32,
+                    device=keys.device)
+    oi = torch.full(keys.shape, -7, dtype=torch.int64, device=keys.device)
+    _call("GammaKTestUnpackKeys", keys.numel(), _p(keys, torch.int64),
+          int(bool(ip)), _p(od), _p(oi))
+    return od, oi
+
+
+def pq_encode(x, codebooks, M, ksub):
+    """x (n, d), codebooks (M, ksub, d/M) -> codes uint8 (n, M)."""
+    assert x.is_contiguous() and codebooks.is_contiguous()
+    n, d = x.shape
+    assert ksub in (16, 256) and d % M == 0
+    assert codebooks.numel() == ksub * d
+    codes = torch.full((n, M), 0xEE, dtype=torch.uint8, device=x.device)
+    _call("GammaKTestPqEncode", n, d, M, ksub, _p(x, torch.float32),
+          _p(codebooks, torch.float32), _p(codes))
+    return codes
+
+
+def pq_encode_pack4(x, codebooks, M):
+    """ksub = 16 encode in packed bucket form -> uint8 (n, M/2)."""
+    assert x.is_contiguous() and codebooks.is_contiguous()
+    n, d = x.shape
+    assert M % 2 == 0 and d % M == 0 and codebooks.numel() == 16 * d
+    codes = torch.full((n, M // 2), 0xEE, dtype=torch.uint8,
+                       device=x.device)
+    _call("GammaKTestPqEncodePack4", n, d, M, _p(x, torch.float32),
+          _p(codebooks, torch.float32), _p(codes))
+    return codes
+
+
+def flat_stream_scan(queries, segs, n, seg_shift, k2, ip, bitmap=None):
+    """FLAT stream scan over n vectors held in `segs` -> (nq, k2) keys."""
+    assert queries.is_contiguous()
+    nq, d = queries.shape
+    assert d % 4 == 0 and 1 <= k2 <= 1024
+    assert len(segs) == (n + (1 << seg_shift) - 1) >> seg_shift
+    table = seg_table(segs)
+    out = torch.full((nq, k2), 0x5A5A5A5A5A5A5A5A, dtype=torch.int64,
+                     device=queries.device)
+    _call("GammaKTestFlatStreamScan", nq, n, d, k2,
+          _p(queries, torch.float32), _p(table), seg_shift,
+          _p(bitmap, torch.int32), int(bool(ip)), _p(out))
+    return out
