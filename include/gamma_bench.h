@@ -82,6 +82,21 @@ int64_t GammaDebugNumDocs(void *engine);
  * [3]=rerank+merge, [4]=D2H, [5]=total wall. Returns 0. */
 int GammaLastSearchTiming(void *engine, double *us6);
 
+/* Compact deleted entries out of the inverted lists (the reference does
+ * this inside Update only — realtime_mem_data.cc:347-370 CompactIfNeed —
+ * and has no C ABI call for it). Every bucket of every vector field's
+ * index whose counted dead entries reach min_ratio of its size is
+ * rewritten without them, order preserved, capacity unchanged;
+ * min_ratio <= 0 means every bucket with at least one dead entry. Takes
+ * the engine's write lock. stats2 (may be NULL), for this call:
+ * [0] = buckets compacted, [1] = entries removed. Returns 0 on success.
+ * AddOrUpdateDoc of an existing key runs the same with min_ratio 0.3. */
+int GammaCompact(void *engine, float min_ratio, int64_t *stats2);
+/* Lifetime totals since the index was created or loaded: [0] = buckets
+ * compacted, [1] = entries removed, and [2] = dead (delete-marked)
+ * entries currently counted in the lists. Summed over vector fields. */
+int GammaCompactStats(void *engine, int64_t *stats3);
+
 /* ---- kernel test hooks (vearch_amd/csrc/ktest.cpp) ----
  * One entry per gk:: host function of csrc/kernels.h, same arguments
  * minus the stream, bool -> int. EVERY pointer is a DEVICE pointer. Each
@@ -121,6 +136,11 @@ int GammaKTestFlatStreamScan(int nq, int64_t n, int d, int k2,
                              const float *queries, const float *const *segs,
                              int seg_shift, const uint32_t *bitmap, int ip,
                              uint64_t *out_keys);
+/* segs_dev: device array of nseg GammaCompactSeg (csrc/kernels.h), i.e.
+ * 8 x 8-byte fields per segment: ids_src, data_src, svals_src (or 0),
+ * size, ids_dst, data_dst, svals_dst (or 0), kept_out. */
+int GammaKTestBucketCompact(int nseg, const void *segs_dev,
+                            const uint32_t *bitmap, int entry_bytes);
 
 #ifdef __cplusplus
 }

@@ -974,6 +974,23 @@ int GammaLastSearchTiming(void *engine, double *us6) {
   return 0;
 }
 
+int GammaCompact(void *engine, float min_ratio, int64_t *stats2) {
+  if (!engine) return -1;
+  int64_t st[2] = {0, 0};
+  int rc = static_cast<Engine *>(engine)->compact(min_ratio, st);
+  if (stats2) {
+    stats2[0] = st[0];
+    stats2[1] = st[1];
+  }
+  return rc;
+}
+
+int GammaCompactStats(void *engine, int64_t *stats3) {
+  if (!engine || !stats3) return -1;
+  static_cast<Engine *>(engine)->compact_stats(stats3);
+  return 0;
+}
+
 /* ------------------------------------------- codec self-tests (CPU-only)
  * Used by tests/test_capi_cpu.py to exercise the hand-written protobuf /
  * FlatBuffers codecs without a GPU. */

@@ -340,6 +340,8 @@ int IVFIndex::init(int d, const IndexParams &p) {
     code_size_ = d * 4;
   }
   buckets_.resize(nlist_);
+  dead_.assign(nlist_, 0);
+  dead_total_ = 0;
   return 0;
 }
 
@@ -713,6 +715,8 @@ int IVFIndex::train(const float *xt, int64_t n, hipStream_t s,
                         btable_.as<float>()) != hipSuccess)
       return -1;
   }
+  dead_.assign(nlist_, 0); /* a fresh model starts with no dead entries */
+  dead_total_ = 0;
   trained_ = true;
   return 0;
 }
@@ -1106,15 +1110,128 @@ int IVFIndex::commit_fast_one(int32_t b, int64_t vid, const float *vec_h,
 int IVFIndex::del(int64_t vid, hipStream_t s) {
   if (vid < 0 || vid >= (int64_t)vid_loc_.size() || vid_loc_[vid] < 0)
     return 0;
+  if (vid_loc_[vid] & kLocDead) return 0; /* already marked + counted */
   int32_t bno = (int32_t)(vid_loc_[vid] >> 40);
-  long long pos = vid_loc_[vid] & (((int64_t)1 << 40) - 1);
+  long long pos = vid_loc_[vid] & kLocPosMask;
   Bucket &bk = buckets_[bno];
   /* device form: bit 31 = the kDelIdxMask bit-63 mark */
   uint32_t marked = (uint32_t)vid | 0x80000000u;
   if (hipMemcpy(bk.ids->as<uint32_t>() + pos, &marked, 4,
                 hipMemcpyHostToDevice) != hipSuccess)
     return -1;
+  vid_loc_[vid] |= kLocDead;
+  dead_[bno]++;
+  dead_total_++;
   return 0;
+}
+
+/* Compactable (realtime_mem_data.cc:366-370): deleted / size >= ratio */
+bool IVFIndex::bucket_compactable_(int b, float min_ratio) const {
+  return dead_[b] > 0 &&
+         (min_ratio <= 0.0f ||
+          (float)dead_[b] / buckets_[b].size >= min_ratio);
+}
+
+bool IVFIndex::compactable(float min_ratio) const {
+  if (dead_total_ == 0) return false;
+  for (int b = 0; b < nlist_; b++)
+    if (bucket_compactable_(b, min_ratio)) return true;
+  return false;
+}
+
+int IVFIndex::compact(float min_ratio, const uint32_t *bitmap_dev,
+                      hipStream_t s, CompactStats *st) {
+  if (!trained_ || !compactable(min_ratio)) return 0;
+  const bool pq = params_.kind == IndexKind::IVFPQ;
+  const size_t entry = pq ? (size_t)code_size_ : (size_t)d_ * 4;
+  std::vector<int> sel;
+  for (int b = 0; b < nlist_; b++)
+    if (bucket_compactable_(b, min_ratio)) sel.push_back(b);
+  const size_t ns = sel.size();
+  /* fresh arrays of the SAME capacity (CompactBucket mallocs
+   * cur_bucket_keys_ entries): a later lock-free append still fits */
+  struct Fresh {
+    std::unique_ptr<DeviceBuf> ids, data, svals;
+  };
+  std::vector<Fresh> fresh(ns);
+  std::vector<GammaCompactSeg> segs(ns);
+  DeviceBuf segs_dev, kept_dev;
+  if (segs_dev.reserve(ns * sizeof(GammaCompactSeg))) return -1;
+  if (kept_dev.reserve(ns * sizeof(long long))) return -1;
+  for (size_t i = 0; i < ns; i++) {
+    Bucket &bk = buckets_[sel[i]];
+    Fresh &f = fresh[i];
+    f.ids = std::make_unique<DeviceBuf>();
+    f.data = std::make_unique<DeviceBuf>();
+    if (f.ids->reserve((size_t)bk.cap * 4)) return -1;
+    if (f.data->reserve((size_t)bk.cap * entry)) return -1;
+    if (pq) {
+      f.svals = std::make_unique<DeviceBuf>();
+      if (f.svals->reserve((size_t)bk.cap * 4)) return -1;
+    }
+    GammaCompactSeg &sg = segs[i];
+    sg.ids_src = bk.ids->as<uint32_t>();
+    sg.data_src = bk.data->as<uint8_t>();
+    sg.svals_src = pq ? bk.svals->as<float>() : nullptr;
+    sg.size = bk.size;
+    sg.ids_dst = f.ids->as<uint32_t>();
+    sg.data_dst = f.data->as<uint8_t>();
+    sg.svals_dst = pq ? f.svals->as<float>() : nullptr;
+    sg.kept_out = kept_dev.as<long long>() + i;
+  }
+  GAMMA_CHECK(hipMemcpyAsync(segs_dev.get(), segs.data(),
+                             ns * sizeof(GammaCompactSeg),
+                             hipMemcpyHostToDevice, s));
+  GAMMA_CHECK(gk::bucket_compact(s, (int)ns, segs_dev.as<GammaCompactSeg>(),
+                                 bitmap_dev, (int)entry));
+  GAMMA_CHECK(hipStreamSynchronize(s));
+  std::vector<long long> kept(ns);
+  GAMMA_CHECK(hipMemcpy(kept.data(), kept_dev.get(), ns * sizeof(long long),
+                        hipMemcpyDeviceToHost));
+  /* read everything back before touching host state, so an error
+   * leaves the index as it was */
+  std::vector<std::vector<uint32_t>> old_ids(ns), new_ids(ns);
+  for (size_t i = 0; i < ns; i++) {
+    Bucket &bk = buckets_[sel[i]];
+    if (kept[i] < 0 || kept[i] > bk.size) return -1;
+    old_ids[i].resize(bk.size);
+    GAMMA_CHECK(hipMemcpy(old_ids[i].data(), bk.ids->get(),
+                          (size_t)bk.size * 4, hipMemcpyDeviceToHost));
+    new_ids[i].resize(kept[i]);
+    if (kept[i] > 0)
+      GAMMA_CHECK(hipMemcpy(new_ids[i].data(), fresh[i].ids->get(),
+                            (size_t)kept[i] * 4, hipMemcpyDeviceToHost));
+  }
+  for (size_t i = 0; i < ns; i++) {
+    const int b = sel[i];
+    Bucket &bk = buckets_[b];
+    /* vid_bucket_no_pos_ rewrite (CompactOne :102): every old entry's
+     * vid drops out, then the survivors get their new positions */
+    for (uint32_t v : old_ids[i]) {
+      size_t vid = v & 0x7fffffffu;
+      if (vid < vid_loc_.size()) vid_loc_[vid] = -1;
+    }
+    for (long long j = 0; j < kept[i]; j++)
+      vid_loc_[new_ids[i][j]] = ((int64_t)b << 40) | j;
+    const long long removed = bk.size - kept[i];
+    bk.ids = std::move(fresh[i].ids);
+    bk.data = std::move(fresh[i].data);
+    if (pq) bk.svals = std::move(fresh[i].svals);
+    bk.size = kept[i];
+    dead_total_ -= dead_[b];
+    dead_[b] = 0;
+    compacted_buckets_++;
+    compacted_entries_ += removed;
+    if (st) {
+      st->buckets++;
+      st->removed += removed;
+    }
+  }
+  /* ntotal_ stays: like the reference's indexed_vec_count_ it counts the
+   * vectors ever indexed (the next-vid cursor Dump/Load carry), which
+   * CompactBucket does not lower; compacted_num_ is the separate tally */
+  dev_buckets_dirty_ = true;
+  return update_dev_buckets(s);
 }
 
 int IVFIndex::coarse_assign(const float *q_dev, int nq, int nprobe, bool ip,
@@ -1399,6 +1516,8 @@ int IVFIndex::load(FILE *f, hipStream_t s) {
     Bucket &bk = buckets_[i];
     bk.size = 0;
     bk.cap = 0;
+    dead_total_ -= dead_[i];
+    dead_[i] = 0;
     if (sz > 0) {
       std::vector<int64_t> ids(sz);
       std::vector<uint8_t> data((size_t)sz * entry);
@@ -1432,6 +1551,9 @@ int IVFIndex::load(FILE *f, hipStream_t s) {
           if (vid >= (int64_t)vid_loc_.size())
             vid_loc_.resize((size_t)vid + 1024, -1);
           vid_loc_[vid] = ((int64_t)i << 40) | j;
+        } else { /* deleted_nums_ rebuilt from the marks (index_io.cc:182) */
+          dead_[i]++;
+          dead_total_++;
         }
       }
     }

@@ -262,7 +262,27 @@ class IVFIndex {
                        float *sval_out);
   int commit_fast_one(int32_t b, int64_t vid, const float *vec_h,
                       const uint8_t *code, float sval, hipStream_t s);
-  int del(int64_t vid, hipStream_t s); /* set bit 63 in the bucket slot */
+  /* set bit 63 in the bucket slot and count the bucket's dead entry;
+   * idempotent per vid (a second del of the same vid is a no-op) */
+  int del(int64_t vid, hipStream_t s);
+  /* Per-bucket compaction (CompactIfNeed/CompactBucket,
+   * realtime_mem_data.cc:94-146, 347-370): every bucket with
+   * dead > 0 && dead / size >= min_ratio (min_ratio <= 0: any dead
+   * entry) is rewritten without its marked / bitmap-deleted entries
+   * into fresh buffers of the same capacity, order preserved, by one
+   * gk::bucket_compact launch; vid_loc_ follows the survivors. Caller
+   * holds the engine write lock. Adds this call's work to *st. */
+  struct CompactStats {
+    int64_t buckets = 0, removed = 0;
+  };
+  int compact(float min_ratio, const uint32_t *bitmap_dev, hipStream_t s,
+              CompactStats *st);
+  /* host counters only: would compact(min_ratio) select any bucket? */
+  bool compactable(float min_ratio) const;
+  /* lifetime totals + entries currently counted dead */
+  int64_t compacted_buckets() const { return compacted_buckets_; }
+  int64_t compacted_entries() const { return compacted_entries_; }
+  int64_t dead_total() const { return dead_total_; }
   /* search: writes keys (nq x k2) into out_keys (device) */
   /* S = probe-split (out_keys must hold nq*S*k2 keys); see
    * probe_split() for the small-batch policy */
@@ -304,6 +324,7 @@ class IVFIndex {
   int encode_entries_(hipStream_t s, int64_t n, const float *resid,
                       uint8_t *codes);
   int update_dev_buckets(hipStream_t s);
+  bool bucket_compactable_(int b, float min_ratio) const;
   /* OPQ-NP training: alternate PQ fit and orthogonal Procrustes
    * (SVD), the algorithm behind faiss OPQMatrix::train (the reference
    * trains/applies it at ivfpq.cc:362-364, 470-471, 585-588) */
@@ -327,8 +348,16 @@ class IVFIndex {
   std::vector<Bucket> buckets_;
   DeviceBuf dev_buckets_; /* GammaBucketDev[nlist] */
   bool dev_buckets_dirty_ = true;
-  /* vid -> (bucket<<40 | pos); -1 = absent. Dense (vids are 0..N). */
+  /* vid -> (bucket<<40 | pos); -1 = absent. Dense (vids are 0..N).
+   * kLocDead is set once the entry carries the delete mark. */
+  static constexpr int64_t kLocDead = (int64_t)1 << 62;
+  static constexpr int64_t kLocPosMask = ((int64_t)1 << 40) - 1;
   std::vector<int64_t> vid_loc_;
+  /* marked entries per bucket (deleted_nums_, realtime_mem_data.cc:
+   * 186-195, 315): counted by del, rebuilt by load, zeroed by compact */
+  std::vector<int64_t> dead_;
+  int64_t dead_total_ = 0;
+  int64_t compacted_buckets_ = 0, compacted_entries_ = 0;
   /* scratch for add/train (grow-only; search scratch lives in
    * SearchScratch so searches can run concurrently) */
   DeviceBuf scratch_i32_, scratch_f32_;
@@ -424,6 +453,16 @@ class Engine {
               const std::vector<MultiVecQuery> *extra_vecs = nullptr);
   int bulk_add(int64_t n, const float *vecs);
   int delete_doc(const std::string &p_key);
+  /* Compact the primary index and every extra vector field's index
+   * under the write lock (no search in flight). stats2 (optional):
+   * buckets compacted, entries removed, summed over the indexes. The
+   * update branch of add_doc calls the same thing with kCompactRatio
+   * (gamma_index_ivfpq.cc:451 CompactIfNeed after Update); a plain
+   * delete_doc only counts. */
+  static constexpr float kCompactRatio = 0.3f; /* realtime_mem_data.cc:369 */
+  int compact(float min_ratio, int64_t *stats2);
+  /* lifetime buckets compacted, entries removed, entries counted dead */
+  void compact_stats(int64_t *stats3) const;
   int build_index(std::string *err);
   /* RebuildIndex (gamma_api.h:103): drop the trained model + lists and
    * retrain from the current raw vectors. */
@@ -570,6 +609,7 @@ class Engine {
                                                bool want_range,
                                                int64_t upto);
   int dump_to_(const std::string &dir, std::string *err);
+  int compact_locked_(float min_ratio, int64_t *stats2); /* write lock held */
   /* lock-free append (caller holds the SHARED lock + append_mu_):
    * 0 = done, 1 = caller must retry under the write lock, -1 error */
   int add_doc_fast_(

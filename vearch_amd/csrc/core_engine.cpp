@@ -148,10 +148,12 @@ int Engine::add_doc(
   }
   std::unique_lock<std::shared_mutex> g(rw_);
   std::lock_guard<std::mutex> ap(append_mu_);
+  bool is_update = false;
   {
     std::lock_guard<std::mutex> pk(pkey_mu_);
     auto it = pkey2docid_.find(p_key);
     if (it != pkey2docid_.end()) {
+      is_update = true;
       /* update = delete old + add new (engine.cc AddOrUpdate
        * semantics) */
       int64_t old = it->second;
@@ -190,6 +192,10 @@ int Engine::add_doc(
     pkey2docid_[p_key] = docid;
   }
   max_docid_.store(docid + 1, std::memory_order_release);
+  /* CompactIfNeed after Update (gamma_index_ivfpq.cc:451,
+   * gamma_index_ivfflat.cc:511): host counters decide, so an update
+   * that crosses no bucket's threshold costs nothing */
+  if (is_update && compact_locked_(kCompactRatio, nullptr)) return -1;
   return 0;
 }
 
@@ -278,6 +284,39 @@ int Engine::delete_doc(const std::string &p_key) {
     if (e->index) e->index->del(it->second, stream_);
   pkey2docid_.erase(it);
   return 0;
+}
+
+int Engine::compact_locked_(float min_ratio, int64_t *stats2) {
+  IVFIndex::CompactStats st;
+  const uint32_t *bm = bitmap_.any() ? bitmap_.dev() : nullptr;
+  if (index_ && index_->compact(min_ratio, bm, stream_, &st)) return -1;
+  for (auto &e : extra_vecs_)
+    if (e->index && e->index->compact(min_ratio, bm, stream_, &st))
+      return -1;
+  if (stats2) {
+    stats2[0] = st.buckets;
+    stats2[1] = st.removed;
+  }
+  return 0;
+}
+
+int Engine::compact(float min_ratio, int64_t *stats2) {
+  if (!table_created_) return -1;
+  std::unique_lock<std::shared_mutex> g(rw_);
+  return compact_locked_(min_ratio, stats2);
+}
+
+void Engine::compact_stats(int64_t *stats3) const {
+  std::shared_lock<std::shared_mutex> g(rw_);
+  stats3[0] = stats3[1] = stats3[2] = 0;
+  auto acc = [&](const IVFIndex *ix) {
+    if (!ix) return;
+    stats3[0] += ix->compacted_buckets();
+    stats3[1] += ix->compacted_entries();
+    stats3[2] += ix->dead_total();
+  };
+  acc(index_.get());
+  for (auto &e : extra_vecs_) acc(e->index.get());
 }
 
 int Engine::build_index(std::string *err) {

@@ -33,7 +33,35 @@ struct GammaScatterSeg {
   long long count;
 };
 
+/* one bucket of a compaction batch (gk::bucket_compact): the first
+ * `size` entries of the *_src arrays are filtered into the *_dst arrays.
+ * Source and destination are different allocations. data_src/data_dst
+ * are aligned to the largest of 16/8/4/1 bytes that divides the entry
+ * size (every hipMalloc'd bucket is). All fields are 8 bytes wide, so a
+ * descriptor is 8 x int64 for callers that build it without this header. */
+struct GammaCompactSeg {
+  const uint32_t *ids_src;
+  const uint8_t *data_src;
+  const float *svals_src; /* null for IVFFLAT */
+  long long size;
+  uint32_t *ids_dst;
+  uint8_t *data_dst;
+  float *svals_dst; /* null for IVFFLAT */
+  long long *kept_out; /* one count per segment */
+};
+
 namespace gk {
+
+/* Stable compaction of a batch of buckets in one launch, the mirror of
+ * bucket_scatter (CompactBucket, realtime_mem_data.cc:94-146). Entry i of
+ * a segment survives iff its id has bit 31 (the delete mark) clear and
+ * `bitmap` (optional docid bitmap, u32 words) does not have bit id set.
+ * Survivors keep their relative order and land at 0..kept-1 of ids_dst /
+ * data_dst / svals_dst; *kept_out = kept; nothing at or beyond kept is
+ * written. size == 0 is legal. entry_bytes may be any positive size. */
+hipError_t bucket_compact(hipStream_t s, int nseg,
+                          const GammaCompactSeg *segs_dev,
+                          const uint32_t *bitmap, int entry_bytes);
 
 /* Bulk bucket append: instead of 3 small hipMemcpys per bucket per
  * chunk (~100k calls per 64k-vector chunk at nlist=32k — the N=50M

@@ -1631,6 +1631,99 @@ hipError_t gk::bucket_scatter(hipStream_t s, int nseg,
   return hipGetLastError();
 }
 
+/* ------------------------------------------------------ bucket compact
+ * Stable out-of-place compaction of IVF lists (CompactBucket/CompactOne,
+ * realtime_mem_data.cc:94-146). One workgroup per segment walks the list
+ * in tiles of WG entries. Per tile: each lane decides keep for its own
+ * entry (mark bit 31 clear and docid bitmap clear), the wave ballot gives
+ * the in-wave rank (popcount of the lower lanes), wave totals meet in LDS
+ * and a running base is carried across tiles, so survivor j of the list
+ * lands at slot j. Ids and S terms are written by the owning lane.
+ * Payloads move as units of T (the widest word dividing entry_bytes);
+ * G = 1 << gshift lanes (the power of two covering one entry's units,
+ * capped at the wave) copy one entry together and 64/G entries go per
+ * pass, survivors taken in rank order through a per-wave rank -> lane
+ * table in LDS — small PQ entries are one unit per lane, an IVFFLAT row
+ * is streamed by the whole wave. Both LDS arrays are double-buffered on
+ * tile parity so one barrier per tile is enough. */
+template <class T>
+__global__ void __launch_bounds__(WG)
+k_bucket_compact(int nseg, const GammaCompactSeg *__restrict__ segs,
+                 const uint32_t *__restrict__ bitmap, int entry_bytes,
+                 int gshift) {
+  __shared__ int wtot[2][WG / 64];
+  __shared__ uint8_t src_lane[2][WG / 64][64];
+  const GammaCompactSeg sg = segs[blockIdx.x];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int units = entry_bytes / (int)sizeof(T);
+  const int slot = lane >> gshift;            /* entry slot in a pass */
+  const int sub = lane & ((1 << gshift) - 1); /* unit lane in the entry */
+  const int per_pass = 64 >> gshift;
+  long long base = 0;
+  int par = 0;
+  for (long long t0 = 0; t0 < sg.size; t0 += WG, par ^= 1) {
+    const long long i = t0 + threadIdx.x;
+    uint32_t id = 0x80000000u;
+    if (i < sg.size) id = sg.ids_src[i];
+    const bool keep =
+        !(id & 0x80000000u) && !gamma_bitmap_test(bitmap, (uint64_t)id);
+    const unsigned long long m = __ballot(keep);
+    const int rank = __popcll(m & ((1ull << lane) - 1ull));
+    const int wkept = __popcll(m);
+    if (keep) src_lane[par][wave][rank] = (uint8_t)lane;
+    if (lane == 0) wtot[par][wave] = wkept;
+    __syncthreads();
+    int before = 0, total = 0;
+    for (int w = 0; w < WG / 64; w++) {
+      int c = wtot[par][w];
+      if (w < wave) before += c;
+      total += c;
+    }
+    const long long wbase = base + before;
+    if (keep) {
+      sg.ids_dst[wbase + rank] = id;
+      if (sg.svals_dst && sg.svals_src)
+        sg.svals_dst[wbase + rank] = sg.svals_src[i];
+    }
+    for (int r = slot; r < wkept; r += per_pass) {
+      const long long si = t0 + wave * 64 + src_lane[par][wave][r];
+      const T *s = (const T *)(sg.data_src + si * entry_bytes);
+      T *d = (T *)(sg.data_dst + (wbase + r) * entry_bytes);
+      for (int j = sub; j < units; j += 1 << gshift) d[j] = s[j];
+    }
+    base += total;
+  }
+  if (threadIdx.x == 0) *sg.kept_out = base;
+}
+
+hipError_t gk::bucket_compact(hipStream_t s, int nseg,
+                              const GammaCompactSeg *segs_dev,
+                              const uint32_t *bitmap, int entry_bytes) {
+  if (entry_bytes <= 0) return hipErrorInvalidValue;
+  if (nseg <= 0) return hipSuccess;
+  const int wbytes = (entry_bytes % 16 == 0)  ? 16
+                     : (entry_bytes % 8 == 0) ? 8
+                     : (entry_bytes % 4 == 0) ? 4
+                                              : 1;
+  int gshift = 0;
+  while (gshift < 6 && (1 << gshift) < entry_bytes / wbytes) gshift++;
+  dim3 g((uint32_t)nseg), b(WG);
+  if (wbytes == 16)
+    k_bucket_compact<uint4><<<g, b, 0, s>>>(nseg, segs_dev, bitmap,
+                                            entry_bytes, gshift);
+  else if (wbytes == 8)
+    k_bucket_compact<uint2><<<g, b, 0, s>>>(nseg, segs_dev, bitmap,
+                                            entry_bytes, gshift);
+  else if (wbytes == 4)
+    k_bucket_compact<uint32_t><<<g, b, 0, s>>>(nseg, segs_dev, bitmap,
+                                               entry_bytes, gshift);
+  else
+    k_bucket_compact<uint8_t><<<g, b, 0, s>>>(nseg, segs_dev, bitmap,
+                                              entry_bytes, gshift);
+  return hipGetLastError();
+}
+
 /* ----------------------------------------------------------- residuals */
 __global__ void k_residuals(int64_t n, int d, const float *__restrict__ x,
                             const float *__restrict__ centroids,

@@ -87,4 +87,11 @@ int GammaKTestFlatStreamScan(int nq, int64_t n, int d, int k2,
                                       seg_shift, bitmap, ip != 0, out_keys));
 }
 
+int GammaKTestBucketCompact(int nseg, const void *segs_dev,
+                            const uint32_t *bitmap, int entry_bytes) {
+  return kt_done(gk::bucket_compact(nullptr, nseg,
+                                    (const GammaCompactSeg *)segs_dev, bitmap,
+                                    entry_bytes));
+}
+
 } /* extern "C" */

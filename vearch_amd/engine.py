@@ -82,6 +82,8 @@ def lib():
         L.GammaDebugNumDocs.argtypes = [c.c_void_p]
         L.GammaLastSearchTiming.argtypes = [c.c_void_p,
                                             c.POINTER(c.c_double)]
+        L.GammaCompact.argtypes = [c.c_void_p, c.c_float, i64p]
+        L.GammaCompactStats.argtypes = [c.c_void_p, i64p]
         _lib = L
     return _lib
 
@@ -195,6 +197,25 @@ class GammaEngine:
         _check(lib().RemoveFieldIndex(self.h, name.encode(),
                                       len(name.encode())),
                "RemoveFieldIndex")
+
+    def compact(self, min_ratio=0.3):
+        """Compact deleted entries out of every inverted list whose dead
+        share is >= min_ratio (<= 0: any dead entry). Returns this
+        call's {"buckets": lists rewritten, "removed": entries dropped}."""
+        st = np.zeros(2, dtype=np.int64)
+        rc = lib().GammaCompact(self.h, float(min_ratio), _ip(st))
+        if rc != 0:
+            raise RuntimeError(f"GammaCompact failed rc={rc}")
+        return {"buckets": int(st[0]), "removed": int(st[1])}
+
+    def compact_stats(self):
+        """Lifetime compaction totals plus the dead entries currently
+        counted: {"buckets", "removed", "dead"}."""
+        st = np.zeros(3, dtype=np.int64)
+        if lib().GammaCompactStats(self.h, _ip(st)) != 0:
+            raise RuntimeError("GammaCompactStats failed")
+        return {"buckets": int(st[0]), "removed": int(st[1]),
+                "dead": int(st[2])}
 
     def num_docs(self):
         return lib().GammaDebugNumDocs(self.h)

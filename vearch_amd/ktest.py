@@ -43,6 +43,7 @@ def _lib():
         L.GammaKTestPqEncodePack4.argtypes = [i64, i32, i32, vp, vp, vp]
         L.GammaKTestFlatStreamScan.argtypes = [
             i32, i64, i32, i32, vp, vp, i32, vp, i32, vp]
+        L.GammaKTestBucketCompact.argtypes = [i32, vp, vp, i32]
         _ready = True
     return L
 
@@ -243,3 +244,51 @@ def flat_stream_scan(queries, segs, n, seg_shift, k2, ip, bitmap=None):
           _p(queries, torch.float32), _p(table), seg_shift,
           _p(bitmap, torch.int32), int(bool(ip)), _p(out))
     return out
+
+
+COMPACT_CANARY_ID = 0x5A5A5A5A
+COMPACT_CANARY_BYTE = 0xA5
+COMPACT_CANARY_SVAL = -7.0
+
+
+def bucket_compact(segments, entry_bytes, bitmap=None):
+    """One gk::bucket_compact launch over `segments`, a list of host
+    (ids uint32 (n,), data uint8 (n, entry_bytes), svals float32 (n,) or
+    None). Every array gets its own device allocation; destinations have
+    the source's length and are pre-filled with the COMPACT_CANARY_*
+    values. bitmap: optional device int32 words (bitmap_to_dev).
+    Returns one (ids uint32, data uint8, svals float32 or None, kept) per
+    segment: the FULL destination arrays, canary tail included."""
+    keep_alive, rows, outs = [], [], []
+    kept = torch.full((max(len(segments), 1),), -7, dtype=torch.int64,
+                      device="cuda")
+    for i, (ids, data, svals) in enumerate(segments):
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        n = ids.shape[0]
+        data = np.ascontiguousarray(data, dtype=np.uint8).reshape(
+            n, entry_bytes)
+        ids_s = torch.from_numpy(ids.view(np.int32).copy()).cuda()
+        data_s = torch.from_numpy(data.copy()).cuda()
+        ids_d = torch.full((n,), COMPACT_CANARY_ID, dtype=torch.int32,
+                           device="cuda")
+        data_d = torch.full((n, entry_bytes), COMPACT_CANARY_BYTE,
+                            dtype=torch.uint8, device="cuda")
+        sv_s = sv_d = None
+        if svals is not None:
+            sv = np.ascontiguousarray(svals, dtype=np.float32)
+            assert sv.shape == (n,)
+            sv_s = torch.from_numpy(sv.copy()).cuda()
+            sv_d = torch.full((n,), COMPACT_CANARY_SVAL,
+                              dtype=torch.float32, device="cuda")
+        keep_alive += [ids_s, data_s, ids_d, data_d, sv_s, sv_d]
+        ptr = lambda t: t.data_ptr() if t is not None and n else 0
+        rows.append([ptr(ids_s), ptr(data_s), ptr(sv_s), n, ptr(ids_d),
+                     ptr(data_d), ptr(sv_d), kept.data_ptr() + 8 * i])
+        outs.append((ids_d, data_d, sv_d))
+    segs = torch.tensor(rows, dtype=torch.int64).reshape(-1, 8).cuda()
+    _call("GammaKTestBucketCompact", len(segments), _p(segs, torch.int64),
+          _p(bitmap, torch.int32), entry_bytes)
+    kept_h = kept.cpu().numpy()
+    return [(i_d.cpu().numpy().view(np.uint32), d_d.cpu().numpy(),
+             None if s_d is None else s_d.cpu().numpy(), int(kept_h[i]))
+            for i, (i_d, d_d, s_d) in enumerate(outs)]
