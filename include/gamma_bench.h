@@ -141,6 +141,29 @@ int GammaKTestFlatStreamScan(int nq, int64_t n, int d, int k2,
  * size, ids_dst, data_dst, svals_dst (or 0), kept_out. */
 int GammaKTestBucketCompact(int nseg, const void *segs_dev,
                             const uint32_t *bitmap, int entry_bytes);
+/* L2 query tables: atab (nq x M x ksub) from gk::pq_tables_a; cwn
+ * (M x ksub codeword norms) from gk::pq_cwn; PqLutL2 writes the table the
+ * 8-bit fast scan's in-kernel builder leaves in LDS (same shape as atab,
+ * bit-identical to it). */
+int GammaKTestPqTablesA(int nq, int d, int M, int ksub, const float *queries,
+                        const float *codebooks, float *atab);
+int GammaKTestPqCwn(int M, int ksub, int dsub, const float *codebooks,
+                    float *cwn);
+int GammaKTestPqLutL2(int nq, int d, int M, int ksub, const float *queries,
+                      const float *codebooks, const float *cwn, float *out);
+/* gk::ivfpq_scan. buckets_dev: device array of nlist GammaBucketDev
+ * (csrc/kernels.h), i.e. 4 x 8-byte fields per list: ids (u32, bit 31 =
+ * deleted), codes, svals, size. out_keys: nq x S x k2. atab / cwn: see
+ * kernels.h (either may be 0 when the launch does not read it); bitmap,
+ * kill_flag, qmap may be 0. */
+int GammaKTestIvfpqScan(int nq, int S, int d, int M, int ksub, int nprobe,
+                        int k2, const float *queries, const float *centroids,
+                        const float *codebooks, const float *atab,
+                        const float *cwn, const float *probe_dists,
+                        const void *buckets_dev, int nlist,
+                        const int64_t *probes, const uint32_t *bitmap, int ip,
+                        uint64_t *out_keys, const int *kill_flag,
+                        const int32_t *qmap);
 
 #ifdef __cplusplus
 }

@@ -567,6 +567,7 @@ int IVFIndex::train_opq_(const float *xt, int64_t n, hipStream_t s,
     if (codebooks_.reserve(books.size() * 4)) return -1;
     GAMMA_CHECK(hipMemcpy(codebooks_.get(), books.data(),
                           books.size() * 4, hipMemcpyHostToDevice));
+    if (update_cwn_(s)) return -1;
     GAMMA_CHECK(gk::pq_encode(s, n_o, d, M_, ksub_, xr.as<float>(),
                               codebooks_.as<float>(),
                               codes_d.as<uint8_t>()));
@@ -709,6 +710,7 @@ int IVFIndex::train(const float *xt, int64_t n, hipStream_t s,
     GAMMA_CHECK(hipMemcpy(codebooks_.get(), books.data(),
                           (size_t)M_ * ksub_ * dsub_ * 4,
                           hipMemcpyHostToDevice));
+    if (update_cwn_(s)) return -1;
     if (btable_.reserve((size_t)nlist_ * M_ * ksub_ * 4)) return -1;
     if (gk::pq_tables_b(s, d_, M_, ksub_, nlist_, centroids_.as<float>(),
                         codebooks_.as<float>(),
@@ -718,6 +720,15 @@ int IVFIndex::train(const float *xt, int64_t n, hipStream_t s,
   dead_.assign(nlist_, 0); /* a fresh model starts with no dead entries */
   dead_total_ = 0;
   trained_ = true;
+  return 0;
+}
+
+/* codeword norms follow the codebooks: call after every write of
+ * codebooks_ (train, the OPQ fit's intermediate books, load) */
+int IVFIndex::update_cwn_(hipStream_t s) {
+  if (cwn_.reserve((size_t)M_ * ksub_ * 4)) return -1;
+  GAMMA_CHECK(gk::pq_cwn(s, M_, ksub_, dsub_, codebooks_.as<float>(),
+                         cwn_.as<float>()));
   return 0;
 }
 
@@ -1326,8 +1337,11 @@ int IVFIndex::search(const float *q_dev, int nq, int k2, int nprobe,
     return -1;
   (void)hipEventRecord(e1, s);
   if (params_.kind == IndexKind::IVFPQ) {
+    /* the 8-bit fast scan builds its L2 query table in LDS from
+     * codebooks_ + cwn_; only the generic and 4-bit kernels still read a
+     * precomputed A table */
     const float *atab = nullptr;
-    if (!metric_ip) {
+    if (!metric_ip && !gk::ivfpq_scan_builds_table(M_, ksub_, k2)) {
       if (sc.atab.reserve((size_t)nq * M_ * ksub_ * 4)) return -1;
       GAMMA_CHECK(gk::pq_tables_a(s, nq, d_, M_, ksub_, q_dev,
                                   codebooks_.as<float>(),
@@ -1377,7 +1391,7 @@ int IVFIndex::search(const float *q_dev, int nq, int k2, int nprobe,
     GAMMA_CHECK(gk::ivfpq_scan(s, nq, S, d_, M_, ksub_, nprobe, k2, q_dev,
                                centroids_.as<float>(),
                                codebooks_.as<float>(), atab,
-                               sc.pdists.as<float>(),
+                               cwn_.as<float>(), sc.pdists.as<float>(),
                                dev_buckets_.as<GammaBucketDev>(), nlist_,
                                sc.probes.as<int64_t>(), bitmap_dev,
                                metric_ip, out_keys_dev, kill_flag_dev,
@@ -1492,6 +1506,7 @@ int IVFIndex::load(FILE *f, hipStream_t s) {
     if (codebooks_.reserve(books.size() * 4)) return -1;
     (void)hipMemcpy(codebooks_.get(), books.data(), books.size() * 4,
               hipMemcpyHostToDevice);
+    if (update_cwn_(s)) return -1;
     if (btable_.reserve((size_t)nlist_ * M_ * ksub_ * 4)) return -1;
     if (gk::pq_tables_b(s, d_, M_, ksub_, nlist_, centroids_.as<float>(),
                         codebooks_.as<float>(),

@@ -336,6 +336,10 @@ class IVFIndex {
   int64_t ntotal_ = 0;
   DeviceBuf centroids_, cent_norms_, codebooks_;
   DeviceBuf btable_; /* pct1 B table: nlist x M x ksub f32 */
+  DeviceBuf cwn_;    /* codeword norms, M x ksub f32 (gk::pq_cwn): derived
+                        from codebooks_ wherever those are written, never
+                        dumped */
+  int update_cwn_(hipStream_t s);
   DeviceBuf opq_R_;  /* d x d rotation, row-major: y_j = R[j] . x */
   std::vector<float> opq_R_host_;
   struct Bucket {

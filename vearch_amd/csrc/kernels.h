@@ -119,6 +119,17 @@ hipError_t pq_tables_b(hipStream_t s, int d, int M, int ksub, int nlist,
 hipError_t pq_tables_a(hipStream_t s, int nq, int d, int M, int ksub,
                        const float *queries, const float *codebooks,
                        float *atab);
+/* cwn[m][j] = ||cw_mj||^2 (M*ksub floats; dsub = d/M), the
+ * query-independent term of atab with pq_tables_a's own fmaf chain.
+ * Derived from the codebooks once per model; the 8-bit fast scan builds
+ * its query table in LDS from it (see ivfpq_scan). */
+hipError_t pq_cwn(hipStream_t s, int M, int ksub, int dsub,
+                  const float *codebooks, float *cwn);
+/* TEST HOOK: out[q][m][j] = the L2 table the fast scan's in-kernel
+ * builder leaves in LDS for query q — bit-identical to pq_tables_a. */
+hipError_t pq_lut_l2_dump(hipStream_t s, int nq, int d, int M, int ksub,
+                          const float *queries, const float *codebooks,
+                          const float *cwn, float *out);
 
 /* Per-vector S term (encode/add/load time):
  *   out[i] = sum_m btab[asg_i][m][code_i[m]]   (plain adds, m order)
@@ -154,11 +165,21 @@ hipError_t pq_sterm_buckets(hipStream_t s, int nlist, int M, int ksub,
  * the ORIGINAL query row. */
 /* ksub=16 runs k_ivfpq_scan4 on packed 4-bit entries (M/2 bytes, low
  * nibble = even sub-quantizer) with an M x 16 table; same contract. */
+/* L2 table source: when ivfpq_scan_builds_table(M, ksub, k2) the kernel
+ * (8-bit codes, M in {16,32,64,96}, k2 + block size within the selector
+ * cap) builds the query table itself from codebooks + cwn (pq_cwn) and
+ * atab may be null; otherwise atab (pq_tables_a) is required and cwn may
+ * be null. Inner product needs neither. Both functions read the same
+ * launch knobs: GAMMA_SCAN_BS (256|512 threads; default 512) and
+ * GAMMA_ADC_C (1|2 codes staged per thread, 4-bit kernel only — the
+ * 8-bit fast path accepts and ignores it). Results do not depend on
+ * either knob. */
+bool ivfpq_scan_builds_table(int M, int ksub, int k2);
 hipError_t ivfpq_scan(hipStream_t s, int nq, int S, int d, int M, int ksub,
                       int nprobe,
                       int k2, const float *queries, const float *centroids,
                       const float *codebooks, const float *atab,
-                      const float *probe_dists,
+                      const float *cwn, const float *probe_dists,
                       const GammaBucketDev *buckets,
                       int nlist, const int64_t *probes,
                       const uint32_t *bitmap, bool ip, uint64_t *out_keys,

@@ -424,19 +424,168 @@ hipError_t gk::argmin_rows(hipStream_t s, int64_t nrows, int ncols,
  * dis = dis0 + sum_m T[m][code_m] in ascending m (plain adds — matches
  * oracle bit-for-bit, see oracle_ivfpq_search_pct1).
  * MW = M/4 compile-time (0 = generic runtime-M path). The templated path
- * stages GAMMA_ADC_C codes per thread in registers with all global loads
- * issued before any use. C=1 measured fastest at BS=512 (9.06 ms vs
- * 9.84 ms for C=2 on the uniform 10M/nprobe=32 microbench; 24 waves/CU
- * already cover the load latency, and C=1 halves the register-staging
- * pressure) — see tools/adc_bench.hip. */
+ * walks its probed lists as one flat index space per chunk of probes and
+ * loads one pass ahead of the LDS gather (see the MW > 0 branch). The
+ * 4-bit kernel below still stages GAMMA_ADC_C codes per thread; C=1
+ * measured fastest at BS=512 (9.06 ms vs 9.84 ms for C=2 on the uniform
+ * 10M/nprobe=32 microbench) — see tools/adc_bench.hip. */
 #define GAMMA_ADC_C_DEFAULT 1
-template <bool IP, int MW, int BS, int CP>
+
+/* cwn[e] = ||cw_e||^2 for the M*ksub codewords of dsub floats each: the
+ * query-independent half of every L2 table entry, computed once per
+ * model. The fmaf chain (and its float4 / scalar split on dsub & 3) is
+ * the one k_pq_atable runs per query, so fmaf(-2, dot, cwn[e]) below
+ * reproduces pq_tables_a bit for bit. */
+__device__ __forceinline__ float gamma_cw_norm(const float *cw, int dsub) {
+  float cwn = 0.0f;
+  if ((dsub & 3) == 0) {
+    for (int t = 0; t < dsub; t += 4) {
+      float4 c4 = *(const float4 *)(cw + t);
+      cwn = fmaf(c4.x, c4.x, cwn);
+      cwn = fmaf(c4.y, c4.y, cwn);
+      cwn = fmaf(c4.z, c4.z, cwn);
+      cwn = fmaf(c4.w, c4.w, cwn);
+    }
+  } else {
+    for (int t = 0; t < dsub; t++) cwn = fmaf(cw[t], cw[t], cwn);
+  }
+  return cwn;
+}
+
+__global__ void k_pq_cwn(int nent, int dsub,
+                         const float *__restrict__ codebooks,
+                         float *__restrict__ cwn) {
+  int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= nent) return;
+  cwn[e] = gamma_cw_norm(codebooks + (size_t)e * dsub, dsub);
+}
+
+hipError_t gk::pq_cwn(hipStream_t s, int M, int ksub, int dsub,
+                      const float *codebooks, float *cwn) {
+  int nent = M * ksub;
+  if (nent <= 0) return hipSuccess;
+  k_pq_cwn<<<dim3((uint32_t)((nent + WG - 1) / WG)), dim3(WG), 0, s>>>(
+      nent, dsub, codebooks, cwn);
+  return hipGetLastError();
+}
+
+/* The L2 query table of one query, built by the whole block into `lut`
+ * (M*ksub floats, usually LDS): lut[e] = fmaf(-2, q_m . cw_e, cwn[e]) with
+ * k_pq_atable's dot chain, so every entry equals pq_tables_a's. `qs` is
+ * the query (d floats; all lanes of a wave read the same sub-vector, an
+ * LDS broadcast), lane e streams codeword e (coalesced, L2-resident).
+ * The caller barriers before reading lut. */
+__device__ __forceinline__ void gamma_build_lut_l2(
+    float *lut, const float *qs, const float *__restrict__ codebooks,
+    const float *__restrict__ cwn, int M, int kb, int dsub) {
+  const int nent = M << kb;
+  for (int e = threadIdx.x; e < nent; e += blockDim.x) {
+    const float *cw = codebooks + (size_t)e * dsub;
+    const float *qm = qs + (e >> kb) * dsub;
+    float dot = 0.0f;
+    if ((dsub & 3) == 0) {
+      for (int t = 0; t < dsub; t += 4) {
+        float4 c4 = *(const float4 *)(cw + t);
+        float4 q4 = *(const float4 *)(qm + t);
+        dot = fmaf(q4.x, c4.x, dot);
+        dot = fmaf(q4.y, c4.y, dot);
+        dot = fmaf(q4.z, c4.z, dot);
+        dot = fmaf(q4.w, c4.w, dot);
+      }
+    } else {
+      for (int t = 0; t < dsub; t++) dot = fmaf(qm[t], cw[t], dot);
+    }
+    lut[e] = fmaf(-2.0f, dot, cwn[e]);
+  }
+}
+
+/* test hook: the table gamma_build_lut_l2 leaves in LDS, per query */
+__global__ void __launch_bounds__(WG)
+k_pq_lut_l2_dump(int d, int M, int kb, const float *__restrict__ queries,
+                 const float *__restrict__ codebooks,
+                 const float *__restrict__ cwn, float *__restrict__ out) {
+  extern __shared__ char smem[];
+  float *lut = (float *)smem;
+  float *qs = lut + ((size_t)M << kb);
+  const int q = blockIdx.x;
+  for (int i = threadIdx.x; i < d; i += blockDim.x)
+    qs[i] = queries[(int64_t)q * d + i];
+  __syncthreads();
+  gamma_build_lut_l2(lut, qs, codebooks, cwn, M, kb, d / M);
+  __syncthreads();
+  for (int e = threadIdx.x; e < (M << kb); e += blockDim.x)
+    out[((int64_t)q * M << kb) + e] = lut[e];
+}
+
+hipError_t gk::pq_lut_l2_dump(hipStream_t s, int nq, int d, int M, int ksub,
+                              const float *queries, const float *codebooks,
+                              const float *cwn, float *out) {
+  if (ksub != 256 && ksub != 16) return hipErrorInvalidValue;
+  size_t smem = ((size_t)M * ksub + d) * 4;
+  if (smem > 160 * 1024) return hipErrorInvalidValue;
+  if (nq <= 0) return hipSuccess;
+  k_pq_lut_l2_dump<<<dim3((uint32_t)nq), dim3(WG), smem, s>>>(
+      d, M, ksub == 256 ? 8 : 4, queries, codebooks, cwn, out);
+  return hipGetLastError();
+}
+
+/* Probe descriptors of the 8-bit fast path. A workgroup walks its probe
+ * subsequence in chunks of at most GAMMA_SCAN_PCH lists; the lists of a
+ * chunk form ONE flat index space [0, total): off[i] is the exclusive
+ * prefix sum of the list sizes, so entry g belongs to the list i with
+ * off[i] <= g < off[i+1]. Invalid probes and empty lists have size 0 and
+ * drop out. The stream pointers carry the global address space, which
+ * makes every list load a global_load (vmcnt only) — a generic pointer
+ * would load with flat_load, which also ticks lgkmcnt and would make each
+ * wait of the LDS gather drain the prefetch. */
+#define GAMMA_SCAN_PCH 32
+typedef const __attribute__((address_space(1))) uint32_t *gamma_gu32p;
+typedef const __attribute__((address_space(1))) uint8_t *gamma_gu8p;
+typedef const __attribute__((address_space(1))) float *gamma_gf32p;
+struct GammaScanChunk {
+  gamma_gu32p ids[GAMMA_SCAN_PCH];
+  gamma_gu8p codes[GAMMA_SCAN_PCH];
+  gamma_gf32p svals[GAMMA_SCAN_PCH];
+  float dis0[GAMMA_SCAN_PCH];
+  int sz[GAMMA_SCAN_PCH];
+  int off[GAMMA_SCAN_PCH + 1];
+  int ncons;    /* probes of the chunk whose flat space fits 31 bits */
+  int kill[2];  /* the kill flag as thread 0 last read it, per parity */
+  int state[2]; /* selector append counter */
+};
+
+/* dynamic LDS of k_ivfpq_scan: table, selector scratch + result, the
+ * query (16-B aligned for the table builder's float4 reads), chunk */
+static size_t gamma_scan8_qs_off(int M, int k2) {
+  size_t o = (size_t)M * 256 * 4 + ((size_t)GAMMA_SORT_CAP + k2) * 8;
+  return (o + 15) / 16 * 16;
+}
+static size_t gamma_scan8_chunk_off(int M, int k2, int d) {
+  return (gamma_scan8_qs_off(M, k2) + (size_t)d * 4 + 7) / 8 * 8;
+}
+static size_t gamma_scan8_smem(int M, int k2, int d) {
+  return gamma_scan8_chunk_off(M, k2, d) + sizeof(GammaScanChunk);
+}
+
+/* one list entry in flight: MW code words, the raw id (bit 31 = skip:
+ * delete mark, or no entry at this flat index), its S term and its
+ * list's dis0 */
+template <int MW>
+struct GammaScanElem {
+  uint32_t w[MW ? MW : 1];
+  uint32_t id;
+  float sv, dis0;
+  bool live; /* false: the lane has no entry in this pass */
+};
+
+template <bool IP, int MW, int BS>
 __global__ void __launch_bounds__(BS)
 k_ivfpq_scan(int nq, int S, int d, int M, int nprobe, int k2,
              const float *__restrict__ queries,
              const float *__restrict__ centroids,
              const float *__restrict__ codebooks,
              const float *__restrict__ atab,
+             const float *__restrict__ cwn,
              const float *__restrict__ probe_dists,
              const GammaBucketDev *__restrict__ buckets, int nlist,
              const int64_t *__restrict__ probes,
@@ -448,12 +597,13 @@ k_ivfpq_scan(int nq, int S, int d, int M, int nprobe, int k2,
   const int ksub = 256;
   const int dsub = d / M;
   float *lut = (float *)smem;                       /* M*ksub */
-  uint64_t *sortbuf = (uint64_t *)(smem + ((size_t)M * ksub * 4 + 7) / 8 * 8);
+  uint64_t *sortbuf = (uint64_t *)(smem + (size_t)M * ksub * 4);
   uint64_t *res = sortbuf + GAMMA_SORT_CAP;
-  float *qs = (float *)(res + k2);                  /* d (IP table build) */
-  float *dis0s = qs + d;                            /* 2 (one per half) */
-  long long *szsh = (long long *)(dis0s + 2);       /* 2 (list sizes) */
-  int *state = (int *)(szsh + 2) + 1;               /* int[2] */
+  const size_t qs_off =
+      ((size_t)M * ksub * 4 + ((size_t)GAMMA_SORT_CAP + k2) * 8 + 15) / 16 * 16;
+  float *qs = (float *)(smem + qs_off);             /* d */
+  GammaScanChunk *ch =
+      (GammaScanChunk *)(smem + (qs_off + (size_t)d * 4 + 7) / 8 * 8);
 
   /* probe-split: S sub-workgroups per query, sub-block handles probes
    * p ≡ sub (mod S); partials merged by sort_rows afterwards. S>1 is
@@ -468,7 +618,7 @@ k_ivfpq_scan(int nq, int S, int d, int M, int nprobe, int k2,
   for (int i = threadIdx.x; i < d; i += blockDim.x) qs[i] = qg[i];
 
   GammaSelector sel;
-  sel.init(sortbuf, res, state, k2);  /* has the barrier qs needs */
+  sel.init(sortbuf, res, ch->state, k2);  /* has the barrier qs needs */
 
   if (IP) {
     /* query-level table T[m][j] = dot(q_m, cw_mj), canonical per entry */
@@ -481,11 +631,17 @@ k_ivfpq_scan(int nq, int S, int d, int M, int nprobe, int k2,
       lut[e] = acc;
     }
     __syncthreads();
+  } else if (MW > 0) {
+    /* L2 fast path: the query-level A table is built here, straight
+     * into LDS, from the codebooks and the per-model codeword norms —
+     * no pq_tables_a launch and no 32 KB/query round trip through HBM.
+     * Entries are bit-identical to pq_tables_a's. The list half of the
+     * decomposition (B) is pre-folded into one float per vector (bucket
+     * svals, gk::pq_sterm): dis = coarse_dis + S_v + sum_m A[m][code_m]. */
+    gamma_build_lut_l2(lut, qs, codebooks, cwn, M, 8, dsub);
+    __syncthreads();
   } else {
-    /* L2: the query-level A table ONCE per workgroup. The list half of
-     * the decomposition (B) is pre-folded into one float per vector
-     * (bucket svals, gk::pq_sterm), so no per-(query,list) table is
-     * ever staged: dis = coarse_dis + S_v + sum_m A[m][code_m]. */
+    /* generic path: the A table comes precomputed (gk::pq_tables_a) */
     const float4 *Aq = (const float4 *)(atab + (size_t)q * M * ksub);
     float4 *lut4 = (float4 *)lut;
     for (int e = threadIdx.x; e < (M * ksub) >> 2; e += blockDim.x)
@@ -493,104 +649,194 @@ k_ivfpq_scan(int nq, int S, int d, int M, int nprobe, int k2,
     __syncthreads();
   }
 
-  /* in-flight kill (is_killed_every<1024> analog, ivfpq.h:927): poll a
-   * device flag between lists with an agent-scope load (L2-served, so a
-   * host write during the kernel is visible — plain loads can stay
-   * L1-stale, microarch §Workgroup dispatch). */
   if (MW > 0) {
-    /* TWO probed lists in flight per workgroup: halves of the block
-     * scan consecutive probes of this sub-workgroup's sequence. At
-     * large nlist a list holds ~N/nlist codes (~600 at the headline
-     * config) — against a 512-thread block that wastes ~30% of the
-     * last pass; 2x(BS/2) halves the tail waste and doubles the
-     * independent HBM streams. Push order changes; the selector's
-     * top-k2 is exact under the (dist,id) total order, so results are
-     * unchanged. */
-    const int C = CP;
-    const int HB = BS / 2;
-    const int half = threadIdx.x >= HB ? 1 : 0;
-    const int tid = threadIdx.x - half * HB;
-    for (int t = 0;; t += 2) {
-      int p0 = sub + t * S;
-      if (p0 >= nprobe) break;
-      if (kill_flag &&
-          __hip_atomic_load(kill_flag, __ATOMIC_RELAXED,
-                            __HIP_MEMORY_SCOPE_AGENT))
-        break;
-      int p = sub + (t + half) * S;
-      int64_t ln = -1;
-      if (p < nprobe) ln = probes[(int64_t)q * nprobe + p];
-      if (ln >= nlist) ln = -1;
-      GammaBucketDev bk;
-      bk.size = 0;
-      if (ln >= 0) bk = buckets[ln];
-      float dis0 = 0.0f;
-      if (IP) {
-        if (tid == 0) { /* dis0 = dot(q, c), canonical order, per half */
-          float acc = 0.0f;
-          if (ln >= 0) {
+    /* Flattened, software-pipelined scan. Thread tid handles flat
+     * entries g = it*BS + tid of the current chunk, so the trip count is
+     * uniform across the block (the selector's barriers stay aligned)
+     * and only a chunk's last pass has idle lanes. The loads of pass
+     * it+1 (code words, id, S term) are issued into a second register
+     * set BEFORE the LDS gather of pass it: a workgroup's HBM latency
+     * runs under its own gather instead of in front of it. The loop is
+     * unrolled by two so the register sets alternate without copies and
+     * the wait in front of each gather is a counted vmcnt that leaves
+     * the prefetch outstanding. Push order differs from a list-by-list
+     * walk; the selector's top-k2 is exact under the (dist,id) total
+     * order, so results are unchanged. */
+    const unsigned tid = threadIdx.x;
+    const int np_sub = sub < nprobe ? (nprobe - sub + S - 1) / S : 0;
+    bool killed = false;
+    for (int c0 = 0; c0 < np_sub && !killed;) {
+      const int cn = min(GAMMA_SCAN_PCH, np_sub - c0);
+      if ((int)tid < cn) { /* one thread per probe of the chunk */
+        const int p = sub + (c0 + (int)tid) * S;
+        int64_t ln = probes[(int64_t)q * nprobe + p];
+        GammaBucketDev bk;
+        bk.ids = nullptr; bk.data = nullptr; bk.svals = nullptr;
+        bk.size = 0;
+        float dis0 = 0.0f;
+        if (ln >= 0 && ln < nlist) {
+          bk = buckets[ln];
+          if (IP) { /* dis0 = dot(q, c), canonical serial order */
             const float *cent = centroids + (size_t)ln * d;
-            for (int e = 0; e < d; e++) acc = fmaf(qs[e], cent[e], acc);
+            for (int e = 0; e < d; e++) dis0 = fmaf(qs[e], cent[e], dis0);
+          } else {
+            /* dis0 = the coarse probe distance (ivfpq.h:255
+             * dis0=coarse_dis); the per-list table half arrives as the
+             * per-vector S term */
+            dis0 = probe_dists[(int64_t)q * nprobe + p];
           }
-          dis0s[half] = acc;
-          szsh[half] = bk.size;
         }
-      } else {
-        /* dis0 = the coarse probe distance (ivfpq.h:255
-         * dis0=coarse_dis); the per-list table half arrives as the
-         * per-vector S term */
-        if (ln >= 0 && p < nprobe)
-          dis0 = probe_dists[(int64_t)q * nprobe + p];
-        if (tid == 0) szsh[half] = bk.size;
+        long long sz = bk.size < 0 ? 0 : bk.size;
+        if (sz > 0x7fffffffll) sz = 0x7fffffffll; /* ids are 31-bit */
+        ch->ids[tid] = (gamma_gu32p)bk.ids;
+        ch->codes[tid] = (gamma_gu8p)bk.data;
+        ch->svals[tid] = (gamma_gf32p)bk.svals;
+        ch->dis0[tid] = dis0;
+        ch->sz[tid] = (int)sz;
+      }
+      if (tid == 0) {
+        /* in-flight kill (is_killed_every<1024> analog, ivfpq.h:927):
+         * agent-scope load (L2-served, so a host write during the kernel
+         * is visible — plain loads can stay L1-stale). ONE thread polls
+         * and the block reads its answer from LDS behind a barrier, so
+         * every thread takes the same exit. */
+        ch->kill[0] = kill_flag
+                          ? __hip_atomic_load(kill_flag, __ATOMIC_RELAXED,
+                                              __HIP_MEMORY_SCOPE_AGENT)
+                          : 0;
+        ch->ncons = cn;
+        ch->off[0] = 0;
       }
       __syncthreads();
-      if (IP) dis0 = dis0s[half];
-      /* both halves iterate in lockstep to the longer list so the
-       * selector's block-wide flush barriers stay aligned */
-      long long maxsz = szsh[0] > szsh[1] ? szsh[0] : szsh[1];
-      const uint32_t *ids = bk.ids;
-      const uint8_t *codes = (const uint8_t *)bk.data;
-      const float *svals = (const float *)bk.svals;
-      for (long long j0 = 0; j0 < maxsz; j0 += (long long)HB * C) {
-        long long jb = j0 + (long long)tid * C;
-        uint32_t w[C][MW ? MW : 1]; /* compile-time bounds -> registers */
-        int64_t idv[C];
-        float sv[C];
-#pragma unroll
-        for (int c = 0; c < C; c++) {
-          long long j = jb + c;
-          if (ln >= 0 && j < bk.size) {
-            idv[c] = (int64_t)(int32_t)ids[j]; /* bit31 -> negative */
-            if (!IP) sv[c] = svals[j];
-            const uint32_t *cw = (const uint32_t *)(codes + (size_t)j * M);
-#pragma unroll
-            for (int mw = 0; mw < MW; mw++) w[c][mw] = cw[mw];
-          } else {
-            idv[c] = -1; /* bit 63 set -> skipped below */
-            sv[c] = 0.0f;
-          }
+      if ((int)tid < cn) {
+        long long cum = 0;
+        for (int u = 0; u <= (int)tid; u++) cum += ch->sz[u];
+        if (cum > 0x7fffffffll) { /* flat space is 31-bit: end the chunk
+                                     before this probe (never the first) */
+          atomicMin(&ch->ncons, (int)tid);
+          cum = 0x7fffffffll;
         }
-#pragma unroll
-        for (int c = 0; c < C; c++) {
-          int64_t id = idv[c];
-          if (!((uint64_t)id >> 63) &&
-              !gamma_bitmap_test(bitmap, (uint64_t)id)) {
-            float dis = IP ? dis0 : dis0 + sv[c];
-            const float *tab = lut;
-#pragma unroll
-            for (int mw = 0; mw < MW; mw++) {
-              uint32_t wv = w[c][mw];
-              dis += tab[wv & 255u];         tab += ksub;
-              dis += tab[(wv >> 8) & 255u];  tab += ksub;
-              dis += tab[(wv >> 16) & 255u]; tab += ksub;
-              dis += tab[wv >> 24];          tab += ksub;
-            }
-            sel.push(gamma_make_key<IP>(dis, (uint32_t)id));
-          }
-        }
-        sel.maybe_flush(blockDim.x * C);
+        ch->off[tid + 1] = (int)cum;
       }
-      __syncthreads(); /* dis0s/szsh rewritten next pair */
+      __syncthreads();
+      killed = ch->kill[0] != 0;
+      const int ncons = ch->ncons;
+      const unsigned total = killed ? 0u : (unsigned)ch->off[ncons];
+      const unsigned niter = (total + BS - 1) / BS;
+      c0 += ncons;
+
+      /* this thread's current list: entries [lstart, lend) */
+      int li = 0;
+      unsigned lstart = 0, lend = (unsigned)ch->off[1];
+      gamma_gu32p pid = ch->ids[0];
+      gamma_gu8p pcodes = ch->codes[0];
+      gamma_gf32p psv = ch->svals[0];
+      float ldis0 = ch->dis0[0];
+
+      /* Nothing is read past a list's size: a lane with no entry left
+       * (g >= total, only in a chunk's last pass) re-reads the chunk's
+       * last entry and is marked dead, instead of skipping its loads.
+       * The loads therefore sit in straight-line code; behind a branch
+       * the compiler's wait in front of the gather has to assume the
+       * prefetch may not have been issued and degrades to vmcnt(0). */
+      auto fetch = [&](GammaScanElem<MW> &e, unsigned it) {
+        const unsigned g0 = it * BS + tid;
+        e.live = g0 < total;
+        const unsigned g = e.live ? g0 : total - 1;
+        if (g >= lend) { /* LDS only */
+          do {
+            li++;
+            lend = (unsigned)ch->off[li + 1];
+          } while (g >= lend);
+          lstart = (unsigned)ch->off[li];
+          pid = ch->ids[li];
+          pcodes = ch->codes[li];
+          psv = ch->svals[li];
+          ldis0 = ch->dis0[li];
+        }
+        const unsigned j = g - lstart;
+        e.id = pid[j];
+        if (!IP) e.sv = psv[j];
+        e.dis0 = ldis0;
+        gamma_gu32p cw = (gamma_gu32p)(pcodes + (size_t)j * (MW * 4));
+#pragma unroll
+        for (int mw = 0; mw < MW; mw++) e.w[mw] = cw[mw];
+      };
+      /* wait for all of an entry's loads (one counted vmcnt; the empty
+       * asm only names the registers). Loads left pending — by a skipped
+       * entry, or by the prefetch past the last pass — would make the
+       * compiler drain the NEXT prefetch as soon as one of their
+       * registers is reused. */
+      auto retire = [&](const GammaScanElem<MW> &e) {
+#pragma unroll
+        for (int mw = 0; mw < MW; mw++) asm volatile("" ::"v"(e.w[mw]));
+        asm volatile("" ::"v"(e.id));
+        if (!IP) asm volatile("" ::"v"(e.sv));
+      };
+      auto consume = [&](const GammaScanElem<MW> &e) {
+        retire(e);
+        if (e.live && !(e.id >> 31) &&
+            !gamma_bitmap_test(bitmap, (uint64_t)e.id)) {
+          float dis = IP ? e.dis0 : e.dis0 + e.sv;
+          const float *tab = lut;
+#pragma unroll
+          for (int mw = 0; mw < MW; mw++) {
+            uint32_t wv = e.w[mw];
+            dis += tab[wv & 255u];         tab += ksub;
+            dis += tab[(wv >> 8) & 255u];  tab += ksub;
+            dis += tab[(wv >> 16) & 255u]; tab += ksub;
+            dis += tab[wv >> 24];          tab += ksub;
+          }
+          sel.push(gamma_make_key<IP>(dis, e.id));
+        }
+      };
+
+      /* Flush check (one barrier). A pass pushes at most BS keys, so
+       * where k2 + 2*BS fits the selector cap the check runs every
+       * second pass with margin 2*BS — half the barriers, at the
+       * headline shape among others — and otherwise every pass with
+       * margin BS. Either way at most `fmargin` pushes separate two
+       * checks (the chunk's closing check below covers an odd last pass),
+       * which is maybe_flush's invariant.
+       * The kill flag is polled every pass, by the rule of the prefetch:
+       * the load is issued in front of it, in straight-line code (a
+       * null flag polls a harmless readable word instead), and its
+       * answer is used only after the gather. On a checking pass thread
+       * 0 posts it in a kill[] slot before the barrier and everyone
+       * reads it right behind the barrier; slots alternate so that one
+       * is next written two barriers later. */
+      const bool flush_each = k2 + 2 * BS > GAMMA_SORT_CAP;
+      const int fmargin = flush_each ? BS : 2 * BS;
+      const int *kf = kill_flag ? kill_flag : (const int *)probes;
+      auto pass = [&](GammaScanElem<MW> &nxt, const GammaScanElem<MW> &cur,
+                      unsigned it_nxt, int slot, bool check) {
+        const int kv = __hip_atomic_load(kf, __ATOMIC_RELAXED,
+                                         __HIP_MEMORY_SCOPE_AGENT);
+        fetch(nxt, it_nxt);
+        consume(cur);
+        asm volatile("" ::"v"(kv)); /* retired in every wave, as above */
+        if (!check) return false;
+        if (tid == 0) ch->kill[slot] = kill_flag ? kv : 0;
+        sel.maybe_flush(fmargin);
+        return ch->kill[slot] != 0;
+      };
+      if (niter > 0) {
+        GammaScanElem<MW> ea, eb;
+        fetch(ea, 0);
+        for (unsigned it = 0; it < niter; it += 2) {
+          if ((killed = pass(eb, ea, it + 1, 0, flush_each))) break;
+          if (it + 1 >= niter) break;
+          if ((killed = pass(ea, eb, it + 2,
+                             flush_each ? 1 : (int)((it >> 1) & 1u), true)))
+            break;
+        }
+        retire(ea);
+        retire(eb);
+      }
+      /* barrier: the chunk is rewritten next round. It doubles as the
+       * flush check an odd last pass skipped, so every chunk starts with
+       * a full margin. */
+      sel.maybe_flush(fmargin);
     }
   } else {
     for (int p = sub; p < nprobe; p += S) {
@@ -609,10 +855,10 @@ k_ivfpq_scan(int nq, int S, int d, int M, int nprobe, int k2,
         if (threadIdx.x == 0) {  /* dis0 = dot(q, c), canonical order */
           float acc = 0.0f;
           for (int e = 0; e < d; e++) acc = fmaf(qs[e], cent[e], acc);
-          dis0s[0] = acc;
+          ch->dis0[0] = acc;
         }
         __syncthreads();
-        dis0 = dis0s[0];
+        dis0 = ch->dis0[0];
       } else {
         dis0 = probe_dists[(int64_t)q * nprobe + p];
       }
@@ -642,7 +888,7 @@ k_ivfpq_scan(int nq, int S, int d, int M, int nprobe, int k2,
         }
         sel.maybe_flush(blockDim.x);
       }
-      if (IP) __syncthreads(); /* dis0s rewritten next list */
+      if (IP) __syncthreads(); /* dis0 slot rewritten next list */
     }
   }
   sel.finish();
@@ -891,102 +1137,118 @@ hipError_t gk::extract_probe0(hipStream_t s, int nq, int nprobe,
   return hipGetLastError();
 }
 
+/* launch knobs shared by the launcher and ivfpq_scan_builds_table.
+ * 512-thread blocks put 24 waves on a CU at the headline LDS/WG (the ADC
+ * gather stream wants ~4 waves/SIMD — microarch §LDS); GAMMA_SCAN_BS=256
+ * overrides for experiments. */
+static int gamma_scan_bs() {
+  const char *e = getenv("GAMMA_SCAN_BS");
+  if (e && (atoi(e) == 256 || atoi(e) == 512)) return atoi(e);
+  return 512;
+}
+/* GAMMA_ADC_C = codes register-staged per thread per flush interval in
+ * the 4-bit kernel (1 or 2). The 8-bit fast path prefetches one
+ * iteration ahead instead and has no C variants: the knob is accepted
+ * there and changes nothing. */
+static int gamma_scan_c() {
+  const char *e = getenv("GAMMA_ADC_C");
+  if (e && (atoi(e) == 1 || atoi(e) == 2)) return atoi(e);
+  return GAMMA_ADC_C_DEFAULT;
+}
+static bool gamma_scan_fast_m(int M) {
+  return M == 16 || M == 32 || M == 64 || M == 96;
+}
+/* 8-bit fast path: one selector push per thread per flush check */
+static bool gamma_scan8_fast(int M, int k2, int BS) {
+  return k2 + BS <= GAMMA_SORT_CAP && gamma_scan_fast_m(M);
+}
+
+bool gk::ivfpq_scan_builds_table(int M, int ksub, int k2) {
+  return ksub == 256 && gamma_scan8_fast(M, k2, gamma_scan_bs());
+}
+
 hipError_t gk::ivfpq_scan(hipStream_t s, int nq, int S, int d, int M,
                           int ksub, int nprobe,
                           int k2, const float *queries,
                           const float *centroids, const float *codebooks,
-                          const float *atab,
+                          const float *atab, const float *cwn,
                           const float *probe_dists,
                           const GammaBucketDev *buckets, int nlist,
                           const int64_t *probes, const uint32_t *bitmap,
                           bool ip, uint64_t *out_keys,
                           const int *kill_flag, const int32_t *qmap) {
   if (ksub != 256 && ksub != 16) return hipErrorInvalidValue;
-  /* table M*ksub floats: 32 KB at M=32/8-bit, 2 KB at M=32/4-bit (small
-   * next to the 16 KB selector scratch) */
-  size_t smem = ((size_t)M * ksub * 4 + 7) / 8 * 8 +
-                (GAMMA_SORT_CAP + k2) * 8 + (d + 2) * 4 +
-                2 * sizeof(long long) + 4 * sizeof(int);
-  if (smem > 160 * 1024) return hipErrorInvalidValue;
-  /* batched path needs flush margin blockDim*C inside the selector cap.
-   * 512-thread blocks put 24 waves on a CU at the same LDS/WG (the ADC
-   * gather stream wants ~4 waves/SIMD — microarch §LDS). */
-  /* BS=256 wins when lists are short (nlist=16384: ~N/nlist codes per
-   * list barely fills 512 threads; 256 halves the tail waste and puts
-   * more independent workgroups on each CU). GAMMA_SCAN_BS overrides
-   * for experiments. */
-  int BS = 512;
-  {
-    const char *e = getenv("GAMMA_SCAN_BS");
-    if (e && (atoi(e) == 256 || atoi(e) == 512)) BS = atoi(e);
-  }
-  /* C = codes register-staged per thread per flush interval: deeper
-   * staging doubles the outstanding VMEM requests per wave — the lever
-   * when short lists (large nlist) cap the per-wave pipelining.
-   * GAMMA_ADC_C overrides; default policy below. */
-  int CSEL = GAMMA_ADC_C_DEFAULT;
-  {
-    const char *e = getenv("GAMMA_ADC_C");
-    if (e && (atoi(e) == 1 || atoi(e) == 2)) CSEL = atoi(e);
-  }
-  bool fast = (k2 + BS * CSEL) <= GAMMA_SORT_CAP &&
-              (M == 16 || M == 32 || M == 64 || M == 96);
-  if (!((k2 + BS * CSEL) <= GAMMA_SORT_CAP)) CSEL = 1;
+  const int BS = gamma_scan_bs();
   dim3 g((uint32_t)nq * (uint32_t)S);
-#define GAMMA_LAUNCH_SCAN_K(KERN, IPV, MWV, BSV, CPV)                     \
-  KERN<IPV, MWV, BSV, CPV><<<g, dim3(BSV), smem, s>>>(                    \
+  if (ksub == 256) {
+    const bool fast = gamma_scan8_fast(M, k2, BS);
+    if (!ip && (fast ? !cwn : !atab)) return hipErrorInvalidValue;
+    const size_t smem = gamma_scan8_smem(M, k2, d);
+    if (smem > 160 * 1024) return hipErrorInvalidValue;
+#define GAMMA_LAUNCH_SCAN(IPV, MWV, BSV)                                  \
+  k_ivfpq_scan<IPV, MWV, BSV><<<g, dim3(BSV), smem, s>>>(                 \
+      nq, S, d, M, nprobe, k2, queries, centroids, codebooks, atab, cwn,  \
+      probe_dists, buckets, nlist, probes, bitmap, out_keys, kill_flag,   \
+      qmap)
+#define GAMMA_LAUNCH_SCAN_BS(IPV, MWV)                                    \
+  do {                                                                    \
+    if (BS == 256) GAMMA_LAUNCH_SCAN(IPV, MWV, 256);                      \
+    else GAMMA_LAUNCH_SCAN(IPV, MWV, 512);                                \
+  } while (0)
+    if (ip) {
+      if (!fast) GAMMA_LAUNCH_SCAN(true, 0, WG);
+      else if (M == 16) GAMMA_LAUNCH_SCAN_BS(true, 4);
+      else if (M == 32) GAMMA_LAUNCH_SCAN_BS(true, 8);
+      else if (M == 64) GAMMA_LAUNCH_SCAN_BS(true, 16);
+      else GAMMA_LAUNCH_SCAN_BS(true, 24);
+    } else {
+      if (!fast) GAMMA_LAUNCH_SCAN(false, 0, WG);
+      else if (M == 16) GAMMA_LAUNCH_SCAN_BS(false, 4);
+      else if (M == 32) GAMMA_LAUNCH_SCAN_BS(false, 8);
+      else if (M == 64) GAMMA_LAUNCH_SCAN_BS(false, 16);
+      else GAMMA_LAUNCH_SCAN_BS(false, 24);
+    }
+#undef GAMMA_LAUNCH_SCAN_BS
+#undef GAMMA_LAUNCH_SCAN
+    return hipGetLastError();
+  }
+  /* 4-bit codes: table M*16 floats (2 KB at M=32, small next to the
+   * 16 KB selector scratch); MW = M/8 words per entry */
+  if (!ip && !atab) return hipErrorInvalidValue;
+  size_t smem = (size_t)M * ksub * 4 + (GAMMA_SORT_CAP + k2) * 8 +
+                (d + 2) * 4 + 2 * sizeof(long long) + 4 * sizeof(int);
+  if (smem > 160 * 1024) return hipErrorInvalidValue;
+  /* batched path needs flush margin blockDim*C inside the selector cap */
+  int CSEL = gamma_scan_c();
+  bool fast = (k2 + BS * CSEL) <= GAMMA_SORT_CAP && gamma_scan_fast_m(M);
+  if (!((k2 + BS * CSEL) <= GAMMA_SORT_CAP)) CSEL = 1;
+#define GAMMA_LAUNCH_SCAN4(IPV, MWV, BSV, CPV)                            \
+  k_ivfpq_scan4<IPV, MWV, BSV, CPV><<<g, dim3(BSV), smem, s>>>(           \
       nq, S, d, M, nprobe, k2, queries, centroids, codebooks, atab,       \
       probe_dists, buckets, nlist, probes, bitmap, out_keys,              \
       kill_flag, qmap)
-#define GAMMA_LAUNCH_SCAN_K_BS(KERN, IPV, MWV)                            \
-  do {                                                                    \
-    if (BS == 256 && CSEL == 2)                                           \
-      GAMMA_LAUNCH_SCAN_K(KERN, IPV, MWV, 256, 2);                        \
-    else if (BS == 256) GAMMA_LAUNCH_SCAN_K(KERN, IPV, MWV, 256, 1);      \
-    else if (CSEL == 2) GAMMA_LAUNCH_SCAN_K(KERN, IPV, MWV, 512, 2);      \
-    else GAMMA_LAUNCH_SCAN_K(KERN, IPV, MWV, 512, 1);                     \
-  } while (0)
-#define GAMMA_LAUNCH_SCAN(IPV, MWV, BSV, CPV)                             \
-  GAMMA_LAUNCH_SCAN_K(k_ivfpq_scan, IPV, MWV, BSV, CPV)
-#define GAMMA_LAUNCH_SCAN_BS(IPV, MWV)                                    \
-  GAMMA_LAUNCH_SCAN_K_BS(k_ivfpq_scan, IPV, MWV)
-#define GAMMA_LAUNCH_SCAN4(IPV, MWV, BSV, CPV)                            \
-  GAMMA_LAUNCH_SCAN_K(k_ivfpq_scan4, IPV, MWV, BSV, CPV)
 #define GAMMA_LAUNCH_SCAN4_BS(IPV, MWV)                                   \
-  GAMMA_LAUNCH_SCAN_K_BS(k_ivfpq_scan4, IPV, MWV)
-  if (ksub == 16) { /* 4-bit codes: MW = M/8 words per entry */
-    if (ip) {
-      if (!fast) GAMMA_LAUNCH_SCAN4(true, 0, WG, 1);
-      else if (M == 16) GAMMA_LAUNCH_SCAN4_BS(true, 2);
-      else if (M == 32) GAMMA_LAUNCH_SCAN4_BS(true, 4);
-      else if (M == 64) GAMMA_LAUNCH_SCAN4_BS(true, 8);
-      else GAMMA_LAUNCH_SCAN4_BS(true, 12);
-    } else {
-      if (!fast) GAMMA_LAUNCH_SCAN4(false, 0, WG, 1);
-      else if (M == 16) GAMMA_LAUNCH_SCAN4_BS(false, 2);
-      else if (M == 32) GAMMA_LAUNCH_SCAN4_BS(false, 4);
-      else if (M == 64) GAMMA_LAUNCH_SCAN4_BS(false, 8);
-      else GAMMA_LAUNCH_SCAN4_BS(false, 12);
-    }
-  } else if (ip) {
-    if (!fast) GAMMA_LAUNCH_SCAN(true, 0, WG, 1);
-    else if (M == 16) GAMMA_LAUNCH_SCAN_BS(true, 4);
-    else if (M == 32) GAMMA_LAUNCH_SCAN_BS(true, 8);
-    else if (M == 64) GAMMA_LAUNCH_SCAN_BS(true, 16);
-    else GAMMA_LAUNCH_SCAN_BS(true, 24);
+  do {                                                                    \
+    if (BS == 256 && CSEL == 2) GAMMA_LAUNCH_SCAN4(IPV, MWV, 256, 2);     \
+    else if (BS == 256) GAMMA_LAUNCH_SCAN4(IPV, MWV, 256, 1);             \
+    else if (CSEL == 2) GAMMA_LAUNCH_SCAN4(IPV, MWV, 512, 2);             \
+    else GAMMA_LAUNCH_SCAN4(IPV, MWV, 512, 1);                            \
+  } while (0)
+  if (ip) {
+    if (!fast) GAMMA_LAUNCH_SCAN4(true, 0, WG, 1);
+    else if (M == 16) GAMMA_LAUNCH_SCAN4_BS(true, 2);
+    else if (M == 32) GAMMA_LAUNCH_SCAN4_BS(true, 4);
+    else if (M == 64) GAMMA_LAUNCH_SCAN4_BS(true, 8);
+    else GAMMA_LAUNCH_SCAN4_BS(true, 12);
   } else {
-    if (!fast) GAMMA_LAUNCH_SCAN(false, 0, WG, 1);
-    else if (M == 16) GAMMA_LAUNCH_SCAN_BS(false, 4);
-    else if (M == 32) GAMMA_LAUNCH_SCAN_BS(false, 8);
-    else if (M == 64) GAMMA_LAUNCH_SCAN_BS(false, 16);
-    else GAMMA_LAUNCH_SCAN_BS(false, 24);
+    if (!fast) GAMMA_LAUNCH_SCAN4(false, 0, WG, 1);
+    else if (M == 16) GAMMA_LAUNCH_SCAN4_BS(false, 2);
+    else if (M == 32) GAMMA_LAUNCH_SCAN4_BS(false, 4);
+    else if (M == 64) GAMMA_LAUNCH_SCAN4_BS(false, 8);
+    else GAMMA_LAUNCH_SCAN4_BS(false, 12);
   }
 #undef GAMMA_LAUNCH_SCAN4_BS
 #undef GAMMA_LAUNCH_SCAN4
-#undef GAMMA_LAUNCH_SCAN_BS
-#undef GAMMA_LAUNCH_SCAN
-#undef GAMMA_LAUNCH_SCAN_K_BS
-#undef GAMMA_LAUNCH_SCAN_K
   return hipGetLastError();
 }
 

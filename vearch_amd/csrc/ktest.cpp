@@ -94,4 +94,38 @@ int GammaKTestBucketCompact(int nseg, const void *segs_dev,
                                     entry_bytes));
 }
 
+int GammaKTestPqTablesA(int nq, int d, int M, int ksub, const float *queries,
+                        const float *codebooks, float *atab) {
+  return kt_done(gk::pq_tables_a(nullptr, nq, d, M, ksub, queries, codebooks,
+                                 atab));
+}
+
+int GammaKTestPqCwn(int M, int ksub, int dsub, const float *codebooks,
+                    float *cwn) {
+  return kt_done(gk::pq_cwn(nullptr, M, ksub, dsub, codebooks, cwn));
+}
+
+int GammaKTestPqLutL2(int nq, int d, int M, int ksub, const float *queries,
+                      const float *codebooks, const float *cwn, float *out) {
+  return kt_done(gk::pq_lut_l2_dump(nullptr, nq, d, M, ksub, queries,
+                                    codebooks, cwn, out));
+}
+
+int GammaKTestIvfpqScan(int nq, int S, int d, int M, int ksub, int nprobe,
+                        int k2, const float *queries, const float *centroids,
+                        const float *codebooks, const float *atab,
+                        const float *cwn, const float *probe_dists,
+                        const void *buckets_dev, int nlist,
+                        const int64_t *probes, const uint32_t *bitmap, int ip,
+                        uint64_t *out_keys, const int *kill_flag,
+                        const int32_t *qmap) {
+  static_assert(sizeof(GammaBucketDev) == 32, "4 x 8-byte fields");
+  return kt_done(gk::ivfpq_scan(nullptr, nq, S, d, M, ksub, nprobe, k2,
+                                queries, centroids, codebooks, atab, cwn,
+                                probe_dists,
+                                (const GammaBucketDev *)buckets_dev, nlist,
+                                probes, bitmap, ip != 0, out_keys, kill_flag,
+                                qmap));
+}
+
 } /* extern "C" */

@@ -44,6 +44,12 @@ def _lib():
         L.GammaKTestFlatStreamScan.argtypes = [
             i32, i64, i32, i32, vp, vp, i32, vp, i32, vp]
         L.GammaKTestBucketCompact.argtypes = [i32, vp, vp, i32]
+        L.GammaKTestPqTablesA.argtypes = [i32, i32, i32, i32, vp, vp, vp]
+        L.GammaKTestPqCwn.argtypes = [i32, i32, i32, vp, vp]
+        L.GammaKTestPqLutL2.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp]
+        L.GammaKTestIvfpqScan.argtypes = [
+            i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp,
+            i32, vp, vp, i32, vp, vp, vp]
         _ready = True
     return L
 
@@ -292,3 +298,103 @@ def bucket_compact(segments, entry_bytes, bitmap=None):
     return [(i_d.cpu().numpy().view(np.uint32), d_d.cpu().numpy(),
              None if s_d is None else s_d.cpu().numpy(), int(kept_h[i]))
             for i, (i_d, d_d, s_d) in enumerate(outs)]
+
+
+def pq_tables_a(queries, codebooks, M, ksub):
+    """gk::pq_tables_a: queries (nq, d), codebooks (M, ksub, d/M) ->
+    atab (nq, M, ksub) f32."""
+    assert queries.is_contiguous() and codebooks.is_contiguous()
+    nq, d = queries.shape
+    assert ksub in (16, 256) and d % M == 0
+    assert codebooks.numel() == ksub * d
+    atab = torch.full((nq, M, ksub), float("nan"), dtype=torch.float32,
+                      device=queries.device)
+    _call("GammaKTestPqTablesA", nq, d, M, ksub, _p(queries, torch.float32),
+          _p(codebooks, torch.float32), _p(atab))
+    return atab
+
+
+def pq_cwn(codebooks, M, ksub):
+    """gk::pq_cwn: codebooks (M, ksub, dsub) -> codeword norms (M, ksub)."""
+    assert codebooks.is_contiguous()
+    dsub = codebooks.numel() // (M * ksub)
+    assert codebooks.numel() == M * ksub * dsub
+    cwn = torch.full((M, ksub), float("nan"), dtype=torch.float32,
+                     device=codebooks.device)
+    _call("GammaKTestPqCwn", M, ksub, dsub, _p(codebooks, torch.float32),
+          _p(cwn))
+    return cwn
+
+
+def pq_lut_l2(queries, codebooks, M, ksub):
+    """The L2 query table the 8-bit fast scan builds in LDS (codeword
+    norms from gk::pq_cwn, then the scan's own table builder), copied out
+    per query: (nq, M, ksub) f32."""
+    assert queries.is_contiguous() and codebooks.is_contiguous()
+    nq, d = queries.shape
+    assert ksub in (16, 256) and d % M == 0
+    assert codebooks.numel() == ksub * d
+    cwn = pq_cwn(codebooks, M, ksub)
+    out = torch.full((nq, M, ksub), float("nan"), dtype=torch.float32,
+                     device=queries.device)
+    _call("GammaKTestPqLutL2", nq, d, M, ksub, _p(queries, torch.float32),
+          _p(codebooks, torch.float32), _p(cwn), _p(out))
+    return out
+
+
+def ivfpq_scan(lists, probes, probe_dists, queries, centroids, codebooks,
+               S, k2, ip, bitmap=None, qmap=None):
+    """One gk::ivfpq_scan launch (8-bit codes) on host arrays.
+    lists: one (ids uint32 (n,), codes uint8 (n, M), svals float32 (n,))
+    per inverted list, n = that list's size (0 is legal); every array gets
+    its own device allocation. probes int64 (nq, nprobe) may hold -1 and
+    ids >= nlist; probe_dists float32 (nq, nprobe). queries (nq, d),
+    centroids (nlist, d), codebooks (M, 256, d/M). bitmap: optional uint32
+    words; qmap: optional int32 (nq,) query schedule.
+    Returns (keys, dists, ids): keys uint64 (nq, S, k2) as the kernel
+    wrote them, and the merge the engine applies to the S partial rows of
+    a query (gk::sort_rows over S*k2 keys), top-k2: dists float32 and ids
+    int64 (nq, k2), -1 / -1 where fewer than k2 candidates exist."""
+    f32 = lambda a: torch.from_numpy(  # noqa: E731
+        np.ascontiguousarray(a, dtype=np.float32).copy()).cuda()
+    q_d, cent_d, cb_d = f32(queries), f32(centroids), f32(codebooks)
+    nq, d = q_d.shape
+    nlist = len(lists)
+    M = cb_d.shape[0]
+    assert cb_d.shape[1] == 256 and cb_d.numel() == 256 * d
+    assert cent_d.shape == (nlist, d)
+    probes = np.ascontiguousarray(probes, dtype=np.int64)
+    nprobe = probes.shape[1]
+    assert probes.shape == (nq, nprobe)
+    pr_d = torch.from_numpy(probes.copy()).cuda()
+    pd_d = f32(probe_dists)
+    assert pd_d.shape == (nq, nprobe)
+    keep, rows = [], []
+    for ids, codes, svals in lists:
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        n = ids.shape[0]
+        codes = np.ascontiguousarray(codes, dtype=np.uint8).reshape(n, M)
+        svals = np.ascontiguousarray(svals, dtype=np.float32)
+        assert svals.shape == (n,)
+        t = [torch.from_numpy(ids.view(np.int32).copy()).cuda(),
+             torch.from_numpy(codes.copy()).cuda(),
+             torch.from_numpy(svals.copy()).cuda()]
+        keep += t
+        rows.append([x.data_ptr() if n else 0 for x in t] + [n])
+    bk_d = torch.tensor(rows, dtype=torch.int64).reshape(-1, 4).cuda()
+    bm_d = None if bitmap is None else bitmap_to_dev(bitmap)
+    qm_d = None
+    if qmap is not None:
+        qm_d = torch.from_numpy(
+            np.ascontiguousarray(qmap, dtype=np.int32).copy()).cuda()
+    atab = None if ip else pq_tables_a(q_d, cb_d, M, 256)
+    cwn = pq_cwn(cb_d, M, 256)
+    keys = torch.full((nq, S, k2), 0x5A5A5A5A5A5A5A5A, dtype=torch.int64,
+                      device="cuda")
+    _call("GammaKTestIvfpqScan", nq, S, d, M, 256, nprobe, k2, _p(q_d),
+          _p(cent_d), _p(cb_d), _p(atab), _p(cwn), _p(pd_d),
+          _p(bk_d, torch.int64), nlist, _p(pr_d, torch.int64),
+          _p(bm_d, torch.int32), int(bool(ip)), _p(keys, torch.int64), None,
+          _p(qm_d, torch.int32))
+    od, oi = sort_rows(keys.reshape(nq, S * k2), k2, ip)
+    return keys_to_np(keys), od.cpu().numpy(), oi.cpu().numpy()
