@@ -97,6 +97,24 @@ int GammaCompact(void *engine, float min_ratio, int64_t *stats2);
  * entries currently counted in the lists. Summed over vector fields. */
 int GammaCompactStats(void *engine, int64_t *stats3);
 
+/* ---- BINARYIVF tables (index_type "BINARYIVF", dimension d in bits,
+ * d % 32 == 0). Vectors and queries are d/8 bytes each, bit i of a vector
+ * = (byte[i>>3] >> (i&7)) & 1; scores are Hamming distances. ----
+ * GammaBulkAddBinary / GammaRawSearchBinary: GammaBulkAdd / GammaRawSearch
+ * on n*d/8 (nq*d/8) bytes; rerank and metric do not apply.
+ * GammaDebugCoarseAssignBinary: top-nprobe centroids by (Hamming, list).
+ * GammaDebugGetBinaryCentroids: nlist*d/8 bytes of binarised centroids.
+ * GammaDebugGetList serves the lists with code_size = d/8. */
+int GammaBulkAddBinary(void *engine, const char *field, int field_len, int n,
+                       const uint8_t *vecs);
+int GammaRawSearchBinary(void *engine, int nq, const uint8_t *xq, int k,
+                         int nprobe, int brute, float *out_dists,
+                         int64_t *out_ids);
+int GammaDebugCoarseAssignBinary(void *engine, int nq, const uint8_t *xq,
+                                 int nprobe, int64_t *out_lists,
+                                 float *out_dists);
+int GammaDebugGetBinaryCentroids(void *engine, uint8_t *centroids);
+
 /* ---- kernel test hooks (vearch_amd/csrc/ktest.cpp) ----
  * One entry per gk:: host function of csrc/kernels.h, same arguments
  * minus the stream, bool -> int. EVERY pointer is a DEVICE pointer. Each
@@ -164,6 +182,22 @@ int GammaKTestIvfpqScan(int nq, int S, int d, int M, int ksub, int nprobe,
                         const int64_t *probes, const uint32_t *bitmap, int ip,
                         uint64_t *out_keys, const int *kill_flag,
                         const int32_t *qmap);
+
+/* BINARYIVF kernels (W = d/32 u32 words per vector, LSB-first bits):
+ * HammingMatrix out[i*n+j] = popcount(Q_i xor B_j) as f32; BinivfScan has
+ * GammaKTestIvfpqScan's bucket / probe / key layout with W words per entry
+ * and svals unused; HammingFlatScan walks a segment table of u32 words. */
+int GammaKTestHammingMatrix(const uint32_t *Q, int nq, const uint32_t *B,
+                            int64_t n, int W, float *out);
+int GammaKTestBinivfScan(int nq, int S, int W, int nprobe, int k2,
+                         const uint32_t *queries, const void *buckets_dev,
+                         int nlist, const int64_t *probes,
+                         const uint32_t *bitmap, uint64_t *out_keys,
+                         const int *kill_flag);
+int GammaKTestHammingFlatScan(int nq, int64_t n, int W, int k2,
+                              const uint32_t *queries,
+                              const uint32_t *const *segs, int seg_shift,
+                              const uint32_t *bitmap, uint64_t *out_keys);
 
 #ifdef __cplusplus
 }

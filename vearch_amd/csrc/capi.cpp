@@ -916,6 +916,53 @@ int GammaDebugCoarseAssign(void *engine, int nq, const float *xq,
   return 0;
 }
 
+/* BINARYIVF: a vector of d bits is d/32 opaque 4-byte words in every
+ * layer below (core.hpp IndexKind), so the byte-typed entry points are the
+ * float-typed ones on the same memory */
+static Engine *binary_engine(void *engine) {
+  auto *e = static_cast<Engine *>(engine);
+  return (e && e->binary()) ? e : nullptr;
+}
+
+int GammaBulkAddBinary(void *engine, const char *field, int field_len, int n,
+                       const uint8_t *vecs) {
+  (void)field;
+  (void)field_len;
+  try {
+    Engine *e = binary_engine(engine);
+    return e ? e->bulk_add(n, (const float *)vecs) : -1;
+  } catch (...) {
+    return -1;
+  }
+}
+
+int GammaRawSearchBinary(void *engine, int nq, const uint8_t *xq, int k,
+                         int nprobe, int brute, float *out_dists,
+                         int64_t *out_ids) {
+  try {
+    Engine *e = binary_engine(engine);
+    if (!e) return -1;
+    return e->search(nq, (const float *)xq, k, nprobe, 0, 0, brute != 0, "",
+                     0, out_dists, out_ids);
+  } catch (...) {
+    return -1;
+  }
+}
+
+int GammaDebugCoarseAssignBinary(void *engine, int nq, const uint8_t *xq,
+                                 int nprobe, int64_t *out_lists,
+                                 float *out_dists) {
+  if (!binary_engine(engine)) return -1;
+  return GammaDebugCoarseAssign(engine, nq, (const float *)xq, nprobe,
+                                out_lists, out_dists);
+}
+
+int GammaDebugGetBinaryCentroids(void *engine, uint8_t *centroids) {
+  Engine *e = binary_engine(engine);
+  if (!e || !e->index() || !centroids) return -1;
+  return e->index()->copy_binary_centroids(centroids, e->stream());
+}
+
 int GammaDebugGetOPQ(void *engine, float *R) {
   if (!engine) return -1;
   auto *e = static_cast<Engine *>(engine);

@@ -323,7 +323,15 @@ int IVFIndex::init(int d, const IndexParams &p) {
     if (p.opq_nsubvector <= 0 || d % p.opq_nsubvector != 0) return -1;
   }
   nlist_ = p.ncentroids;
-  if (params_.kind == IndexKind::IVFPQ) {
+  if (params_.kind == IndexKind::BINARYIVF) {
+    /* d is in bits; entries, queries and centroids are d/32 whole words */
+    if (d < 32 || d > 4096 || d % 32 != 0) return -1;
+    bits_ = d;
+    d_ = d / 32;
+    M_ = 0;
+    dsub_ = 0;
+    code_size_ = d / 8;
+  } else if (params_.kind == IndexKind::IVFPQ) {
     M_ = p.nsubvector > 0 ? p.nsubvector : d / 2; /* ivfpq.cc:122-124 */
     if (M_ <= 0 || d % M_ != 0 || M_ % 4 != 0) return -1;
     dsub_ = d / M_;
@@ -345,30 +353,30 @@ int IVFIndex::init(int d, const IndexParams &p) {
   return 0;
 }
 
-int IVFIndex::kmeans_gpu(const float *x_host, int64_t n, int ncl, int niter,
-                         bool spherical, std::vector<float> &cent_out,
+int IVFIndex::kmeans_gpu(const float *x_host, int64_t n, int dim, int ncl,
+                         int niter, bool spherical, std::vector<float> &cent_out,
                          hipStream_t s) {
   /* Lloyd, faiss-Clustering style (ivfpq.cc:188-191): random-sample init,
    * largest-cluster split for empties, optional spherical renorm. */
   DeviceBuf xd, xnorm, cd, cnorm, dots, asg;
-  GAMMA_CHECK(xd.reserve((size_t)n * d_ * 4) ? hipErrorOutOfMemory
+  GAMMA_CHECK(xd.reserve((size_t)n * dim * 4) ? hipErrorOutOfMemory
                                              : hipSuccess);
-  GAMMA_CHECK(hipMemcpy(xd.get(), x_host, (size_t)n * d_ * 4,
+  GAMMA_CHECK(hipMemcpy(xd.get(), x_host, (size_t)n * dim * 4,
                         hipMemcpyHostToDevice));
   GAMMA_CHECK(xnorm.reserve((size_t)n * 4) ? hipErrorOutOfMemory
                                            : hipSuccess);
-  GAMMA_CHECK(gk::row_norms(s, xd.as<float>(), n, d_, xnorm.as<float>()));
+  GAMMA_CHECK(gk::row_norms(s, xd.as<float>(), n, dim, xnorm.as<float>()));
   const int64_t chunk = 16384;
   GAMMA_CHECK(dots.reserve((size_t)std::min(n, chunk) * ncl * 4)
                   ? hipErrorOutOfMemory
                   : hipSuccess);
   GAMMA_CHECK(asg.reserve((size_t)n * 4) ? hipErrorOutOfMemory : hipSuccess);
-  GAMMA_CHECK(cd.reserve((size_t)ncl * d_ * 4) ? hipErrorOutOfMemory
+  GAMMA_CHECK(cd.reserve((size_t)ncl * dim * 4) ? hipErrorOutOfMemory
                                                : hipSuccess);
   GAMMA_CHECK(cnorm.reserve((size_t)ncl * 4) ? hipErrorOutOfMemory
                                              : hipSuccess);
 
-  cent_out.resize((size_t)ncl * d_);
+  cent_out.resize((size_t)ncl * dim);
   std::mt19937_64 rng(42);
   std::vector<int64_t> perm(n);
   for (int64_t i = 0; i < n; i++) perm[i] = i;
@@ -377,34 +385,34 @@ int IVFIndex::kmeans_gpu(const float *x_host, int64_t n, int ncl, int niter,
   }
   for (int c = 0; c < ncl; c++) {
     int64_t src = perm[c % n];
-    memcpy(cent_out.data() + (size_t)c * d_, x_host + (size_t)src * d_,
-           (size_t)d_ * 4);
+    memcpy(cent_out.data() + (size_t)c * dim, x_host + (size_t)src * dim,
+           (size_t)dim * 4);
   }
   auto renorm = [&](std::vector<float> &cent) {
     if (!spherical) return;
     for (int c = 0; c < ncl; c++) {
       double nn = 0;
-      float *row = cent.data() + (size_t)c * d_;
-      for (int j = 0; j < d_; j++) nn += (double)row[j] * row[j];
+      float *row = cent.data() + (size_t)c * dim;
+      for (int j = 0; j < dim; j++) nn += (double)row[j] * row[j];
       float inv = (float)(1.0 / std::max(sqrt(nn), 1e-20));
-      for (int j = 0; j < d_; j++) row[j] *= inv;
+      for (int j = 0; j < dim; j++) row[j] *= inv;
     }
   };
   renorm(cent_out);
 
   std::vector<int32_t> assign_h(n);
-  std::vector<double> sums((size_t)ncl * d_);
+  std::vector<double> sums((size_t)ncl * dim);
   std::vector<int64_t> counts(ncl);
 
   for (int it = 0; it < niter; it++) {
-    GAMMA_CHECK(hipMemcpy(cd.get(), cent_out.data(), (size_t)ncl * d_ * 4,
+    GAMMA_CHECK(hipMemcpy(cd.get(), cent_out.data(), (size_t)ncl * dim * 4,
                           hipMemcpyHostToDevice));
-    GAMMA_CHECK(gk::row_norms(s, cd.as<float>(), ncl, d_,
+    GAMMA_CHECK(gk::row_norms(s, cd.as<float>(), ncl, dim,
                               cnorm.as<float>()));
     for (int64_t r0 = 0; r0 < n; r0 += chunk) {
       int64_t rn = std::min(chunk, n - r0);
-      GAMMA_CHECK(gk::dots_mfma(s, xd.as<float>() + (size_t)r0 * d_, (int)rn,
-                                cd.as<float>(), ncl, d_, dots.as<float>()));
+      GAMMA_CHECK(gk::dots_mfma(s, xd.as<float>() + (size_t)r0 * dim, (int)rn,
+                                cd.as<float>(), ncl, dim, dots.as<float>()));
       GAMMA_CHECK(gk::argmin_rows(s, rn, ncl, dots.as<float>(),
                                   xnorm.as<float>() + r0, cnorm.as<float>(),
                                   !spherical, asg.as<int32_t>() + r0));
@@ -415,9 +423,9 @@ int IVFIndex::kmeans_gpu(const float *x_host, int64_t n, int ncl, int niter,
     std::fill(counts.begin(), counts.end(), 0);
     for (int64_t i = 0; i < n; i++) {
       int c = assign_h[i];
-      const float *row = x_host + (size_t)i * d_;
-      double *srow = sums.data() + (size_t)c * d_;
-      for (int j = 0; j < d_; j++) srow[j] += row[j];
+      const float *row = x_host + (size_t)i * dim;
+      double *srow = sums.data() + (size_t)c * dim;
+      for (int j = 0; j < dim; j++) srow[j] += row[j];
       counts[c]++;
     }
     for (int c = 0; c < ncl; c++) {
@@ -425,11 +433,11 @@ int IVFIndex::kmeans_gpu(const float *x_host, int64_t n, int ncl, int niter,
         int big = (int)(std::max_element(counts.begin(), counts.end()) -
                         counts.begin());
         if (counts[big] < 2) continue;
-        for (int j = 0; j < d_; j++) {
-          double mean = sums[(size_t)big * d_ + j] / counts[big];
+        for (int j = 0; j < dim; j++) {
+          double mean = sums[(size_t)big * dim + j] / counts[big];
           double eps = 1e-5 * (1.0 + fabs(mean));
-          sums[(size_t)c * d_ + j] = (mean + eps) * (counts[big] / 2);
-          sums[(size_t)big * d_ + j] =
+          sums[(size_t)c * dim + j] = (mean + eps) * (counts[big] / 2);
+          sums[(size_t)big * dim + j] =
               (mean - eps) * (counts[big] - counts[big] / 2);
         }
         counts[c] = counts[big] / 2;
@@ -437,9 +445,9 @@ int IVFIndex::kmeans_gpu(const float *x_host, int64_t n, int ncl, int niter,
       }
     }
     for (int c = 0; c < ncl; c++) {
-      float *row = cent_out.data() + (size_t)c * d_;
-      for (int j = 0; j < d_; j++)
-        row[j] = (float)(sums[(size_t)c * d_ + j] /
+      float *row = cent_out.data() + (size_t)c * dim;
+      for (int j = 0; j < dim; j++)
+        row[j] = (float)(sums[(size_t)c * dim + j] /
                          std::max<int64_t>(counts[c], 1));
     }
     renorm(cent_out);
@@ -628,6 +636,7 @@ int IVFIndex::train_opq_(const float *xt, int64_t n, hipStream_t s,
 
 int IVFIndex::train(const float *xt, int64_t n, hipStream_t s,
                     std::string *err) {
+  if (binary()) return train_binary_((const uint32_t *)xt, n, s, err);
   std::vector<float> xrot_h;
   if (has_opq()) {
     /* train R, then train the IVFPQ model in rotated space
@@ -645,7 +654,7 @@ int IVFIndex::train(const float *xt, int64_t n, hipStream_t s,
     xt = xrot_h.data();
   }
   std::vector<float> cent;
-  if (kmeans_gpu(xt, n, nlist_, 10, params_.metric_ip, cent, s)) {
+  if (kmeans_gpu(xt, n, d_, nlist_, 10, params_.metric_ip, cent, s)) {
     if (err) *err = "coarse k-means failed";
     return -1;
   }
@@ -720,6 +729,85 @@ int IVFIndex::train(const float *xt, int64_t n, hipStream_t s,
   dead_.assign(nlist_, 0); /* a fresh model starts with no dead entries */
   dead_total_ = 0;
   trained_ = true;
+  return 0;
+}
+
+int IVFIndex::train_binary_(const uint32_t *x, int64_t n, hipStream_t s,
+                            std::string *err) {
+  const int W = d_;
+  std::vector<float> xf((size_t)n * bits_);
+  for (int64_t i = 0; i < n; i++) {
+    const uint32_t *row = x + (size_t)i * W;
+    float *o = xf.data() + (size_t)i * bits_;
+    for (int b = 0; b < bits_; b++)
+      o[b] = ((row[b >> 5] >> (b & 31)) & 1u) ? 1.0f : -1.0f;
+  }
+  std::vector<float> cent;
+  if (kmeans_gpu(xf.data(), n, bits_, nlist_, 10, false, cent, s)) {
+    if (err) *err = "coarse k-means failed";
+    return -1;
+  }
+  std::vector<uint32_t> cw((size_t)nlist_ * W, 0u);
+  for (int c = 0; c < nlist_; c++)
+    for (int b = 0; b < bits_; b++)
+      if (cent[(size_t)c * bits_ + b] > 0.0f)
+        cw[(size_t)c * W + (b >> 5)] |= 1u << (b & 31);
+  if (centroids_.reserve(cw.size() * 4)) return -1;
+  GAMMA_CHECK(hipMemcpy(centroids_.get(), cw.data(), cw.size() * 4,
+                        hipMemcpyHostToDevice));
+  dead_.assign(nlist_, 0);
+  dead_total_ = 0;
+  trained_ = true;
+  return 0;
+}
+
+int IVFIndex::copy_binary_centroids(uint8_t *out, hipStream_t s) const {
+  (void)s;
+  if (!trained_ || !binary()) return -1;
+  GAMMA_CHECK(hipMemcpy(out, centroids_.get(), (size_t)nlist_ * d_ * 4,
+                        hipMemcpyDeviceToHost));
+  return 0;
+}
+
+/* nearest list per row. Float kinds: GEMM + argmin over the norm form.
+ * BINARYIVF: Hamming matrix, then the top-1 of the ascending (dist, list)
+ * key — ties to the lowest list number — through the existing selector
+ * (argmin_rows without the norm form is an argmax). dots holds
+ * min(n, 16384) x nlist floats; scratch_i32_/scratch_f32_ carry the
+ * binary path's one key, id and distance per row. */
+int IVFIndex::assign_rows_(const float *x_dev, const float *xnorm_dev,
+                           int64_t n, DeviceBuf &dots, int32_t *asg_dev,
+                           hipStream_t s) {
+  const int64_t sub = 16384;
+  if (dots.reserve((size_t)std::min(n, sub) * nlist_ * 4)) return -1;
+  if (binary()) {
+    if (scratch_i32_.reserve((size_t)std::min(n, sub) * 16)) return -1;
+    if (scratch_f32_.reserve((size_t)std::min(n, sub) * 4)) return -1;
+  }
+  for (int64_t r0 = 0; r0 < n; r0 += sub) {
+    int64_t rn = std::min(sub, n - r0);
+    if (binary()) {
+      uint64_t *keys = scratch_i32_.as<uint64_t>();
+      int64_t *ids = (int64_t *)(keys + std::min(n, sub));
+      GAMMA_CHECK(gk::hamming_matrix(
+          s, (const uint32_t *)x_dev + (size_t)r0 * d_, (int)rn,
+          centroids_.as<uint32_t>(), nlist_, d_, dots.as<float>()));
+      GAMMA_CHECK(gk::select_from_dots(s, (int)rn, nlist_, 0, nlist_,
+                                       dots.as<float>(), nullptr, nullptr,
+                                       false, false, nullptr, 1, keys,
+                                       false));
+      GAMMA_CHECK(gk::unpack_keys(s, rn, keys, false,
+                                  scratch_f32_.as<float>(), ids));
+      GAMMA_CHECK(gk::extract_probe0(s, (int)rn, 1, ids, asg_dev + r0));
+    } else {
+      GAMMA_CHECK(gk::dots_mfma(s, x_dev + (size_t)r0 * d_, (int)rn,
+                                centroids_.as<float>(), nlist_, d_,
+                                dots.as<float>()));
+      GAMMA_CHECK(gk::argmin_rows(s, rn, nlist_, dots.as<float>(),
+                                  xnorm_dev + r0, cent_norms_.as<float>(),
+                                  !params_.metric_ip, asg_dev + r0));
+    }
+  }
   return 0;
 }
 
@@ -857,23 +945,13 @@ int IVFIndex::add(const float *x_host, const int64_t *vids, int64_t n,
       if (rotate_dev(xin, cn, xrot.as<float>(), s)) return -1;
       xin = xrot.as<float>();
     }
-    if (xnorm.reserve((size_t)cn * 4)) return -1;
-    (void)gk::row_norms(s, xin, cn, d_, xnorm.as<float>());
-    const int64_t sub = 16384;
-    if (dots.reserve((size_t)std::min(cn, sub) * nlist_ * 4)) return -1;
-    if (asg.reserve((size_t)cn * 4)) return -1;
-    for (int64_t r0 = 0; r0 < cn; r0 += sub) {
-      int64_t rn = std::min(sub, cn - r0);
-      if (gk::dots_mfma(s, xin + (size_t)r0 * d_, (int)rn,
-                        centroids_.as<float>(), nlist_, d_,
-                        dots.as<float>()) != hipSuccess)
-        return -1;
-      if (gk::argmin_rows(s, rn, nlist_, dots.as<float>(),
-                          xnorm.as<float>() + r0, cent_norms_.as<float>(),
-                          !params_.metric_ip,
-                          asg.as<int32_t>() + r0) != hipSuccess)
-        return -1;
+    if (!binary()) { /* binary rows are words: no norms */
+      if (xnorm.reserve((size_t)cn * 4)) return -1;
+      (void)gk::row_norms(s, xin, cn, d_, xnorm.as<float>());
     }
+    if (asg.reserve((size_t)cn * 4)) return -1;
+    if (assign_rows_(xin, xnorm.as<float>(), cn, dots, asg.as<int32_t>(), s))
+      return -1;
     (void)hipMemcpy(asg_h.data(), asg.get(), (size_t)cn * 4,
               hipMemcpyDeviceToHost);
 
@@ -1020,6 +1098,7 @@ int IVFIndex::prepare_fast_one(const float *vec_h, hipStream_t s,
                                int32_t *out_bucket, uint8_t *code_out,
                                float *sval_out) {
   if (!trained_) return 1;
+  if (binary()) return 1; /* binary appends always take the write lock */
   if (dev_buckets_dirty_) return 1; /* device table stale: slow path
                                        rebuilds it under the write lock */
   /* persistent grow-only scratch: a hipFree here would synchronize the
@@ -1257,21 +1336,32 @@ int IVFIndex::coarse_assign(const float *q_dev, int nq, int nprobe, bool ip,
   const bool full_sort = nlist_ <= 512;
   if (!full_sort && sc.sel_keys.reserve((size_t)nq * nprobe * 8))
     return -1;
+  /* BINARYIVF: the matrix holds Hamming distances, selected as they are
+   * in ascending (dist, list) order — no norms, never the IP order */
+  const bool bin = binary();
+  if (bin) ip = false;
   for (int64_t r0 = 0; r0 < nq; r0 += sub) {
     int64_t rn = std::min<int64_t>(sub, nq - r0);
-    GAMMA_CHECK(gk::dots_mfma(s, q_dev + (size_t)r0 * d_, (int)rn,
-                              centroids_.as<float>(), nlist_, d_,
-                              sc.dots.as<float>()));
+    if (bin)
+      GAMMA_CHECK(gk::hamming_matrix(
+          s, (const uint32_t *)q_dev + (size_t)r0 * d_, (int)rn,
+          centroids_.as<uint32_t>(), nlist_, d_, sc.dots.as<float>()));
+    else
+      GAMMA_CHECK(gk::dots_mfma(s, q_dev + (size_t)r0 * d_, (int)rn,
+                                centroids_.as<float>(), nlist_, d_,
+                                sc.dots.as<float>()));
     if (full_sort) {
       GAMMA_CHECK(gk::select_rows_full(
           s, (int)rn, nlist_, nlist_, sc.dots.as<float>(),
-          q_norms_dev + r0, cent_norms_.as<float>(), !ip, ip, nprobe,
+          bin ? nullptr : q_norms_dev + r0, cent_norms_.as<float>(),
+          !ip && !bin, ip, nprobe,
           probe_dists_dev + (size_t)r0 * nprobe,
           probes_dev + (size_t)r0 * nprobe));
     } else {
       GAMMA_CHECK(gk::select_from_dots(
           s, (int)rn, nlist_, 0, nlist_, sc.dots.as<float>(),
-          q_norms_dev + r0, cent_norms_.as<float>(), !ip, ip, nullptr,
+          bin ? nullptr : q_norms_dev + r0, cent_norms_.as<float>(),
+          !ip && !bin, ip, nullptr,
           nprobe, sc.sel_keys.as<uint64_t>() + (size_t)r0 * nprobe,
           false));
     }
@@ -1287,7 +1377,7 @@ int IVFIndex::probe_split(int nq, int k2, int nprobe) const {
   /* small batches underfill the 256 CUs with one WG per query: split
    * probes across S sub-workgroups (merged by sort_rows; S*k2 <= 2048
    * keeps the merge a single row sort) */
-  if (params_.kind != IndexKind::IVFPQ) return 1;
+  if (params_.kind != IndexKind::IVFPQ && !binary()) return 1;
   const char *force = getenv("GAMMA_SCAN_S"); /* perf experiments */
   if (force && atoi(force) > 0) {
     int S = atoi(force);
@@ -1396,6 +1486,12 @@ int IVFIndex::search(const float *q_dev, int nq, int k2, int nprobe,
                                sc.probes.as<int64_t>(), bitmap_dev,
                                metric_ip, out_keys_dev, kill_flag_dev,
                                qmap_dev));
+  } else if (binary()) {
+    GAMMA_CHECK(gk::binivf_scan(s, nq, S, d_, nprobe, k2,
+                                (const uint32_t *)q_dev,
+                                dev_buckets_.as<GammaBucketDev>(), nlist_,
+                                sc.probes.as<int64_t>(), bitmap_dev,
+                                out_keys_dev, kill_flag_dev));
   } else {
     GAMMA_CHECK(gk::ivfflat_scan(s, nq, d_, nprobe, k2, q_dev,
                                  dev_buckets_.as<GammaBucketDev>(), nlist_,
@@ -1497,9 +1593,11 @@ int IVFIndex::load(FILE *f, hipStream_t s) {
   if (centroids_.reserve(cent.size() * 4)) return -1;
   (void)hipMemcpy(centroids_.get(), cent.data(), cent.size() * 4,
             hipMemcpyHostToDevice);
-  if (cent_norms_.reserve((size_t)nlist_ * 4)) return -1;
-  (void)gk::row_norms(s, centroids_.as<float>(), nlist_, d_,
-                cent_norms_.as<float>());
+  if (!binary()) { /* binary centroids are words: no norms */
+    if (cent_norms_.reserve((size_t)nlist_ * 4)) return -1;
+    (void)gk::row_norms(s, centroids_.as<float>(), nlist_, d_,
+                  cent_norms_.as<float>());
+  }
   if (params_.kind == IndexKind::IVFPQ) {
     std::vector<float> books((size_t)M_ * ksub_ * dsub_);
     if (fread(books.data(), 4, books.size(), f) != books.size()) return -1;

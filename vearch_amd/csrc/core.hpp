@@ -191,7 +191,14 @@ class Bitmap {
   int64_t set_count_ = 0;
 };
 
-enum class IndexKind { FLAT, IVFPQ, IVFFLAT };
+/* BINARYIVF (gamma_index_binary_ivf.cc): vectors of d BITS, Hamming
+ * distance. With d % 32 == 0 a vector is W = d/32 opaque 4-byte words, and
+ * that is how every storage layer below sees it: the raw store, the list
+ * entries and the centroids of a binary table are rows of W words held in
+ * the same float-typed buffers the other kinds use (only copied, never
+ * computed on). The vector width the Engine and IVFIndex carry for such a
+ * table is therefore W; the bit count is kept next to it. */
+enum class IndexKind { FLAT, IVFPQ, IVFFLAT, BINARYIVF };
 
 struct IndexParams {
   IndexKind kind = IndexKind::IVFPQ;
@@ -242,8 +249,12 @@ struct SearchScratch {
 
 class IVFIndex {
  public:
+  /* d: vector dimension (BINARYIVF: in bits, a multiple of 32) */
   int init(int d, const IndexParams &p);
   bool trained() const { return trained_; }
+  bool binary() const { return params_.kind == IndexKind::BINARYIVF; }
+  /* BINARYIVF: nlist x d/8 bytes of binarised centroids */
+  int copy_binary_centroids(uint8_t *out, hipStream_t s) const;
   int train(const float *xt, int64_t n, hipStream_t s, std::string *err);
   int add(const float *x_host, const int64_t *vids, int64_t n,
           hipStream_t s);
@@ -315,9 +326,16 @@ class IVFIndex {
   int load(FILE *f, hipStream_t s);
 
  private:
-  int kmeans_gpu(const float *x_host, int64_t n, int ncl, int niter,
-                 bool spherical, std::vector<float> &cent_out,
+  int kmeans_gpu(const float *x_host, int64_t n, int dim, int ncl,
+                 int niter, bool spherical, std::vector<float> &cent_out,
                  hipStream_t s);
+  /* BINARYIVF (faiss IndexBinaryIVF::train): k-means on the +-1 expansion
+   * of the words, centroids binarised by > 0 */
+  int train_binary_(const uint32_t *x, int64_t n, hipStream_t s,
+                    std::string *err);
+  /* argmin list per row: float GEMM + norms, or the Hamming matrix */
+  int assign_rows_(const float *x_dev, const float *xnorm_dev, int64_t n,
+                   DeviceBuf &dots, int32_t *asg_dev, hipStream_t s);
   int pq_subspace_kmeans_(const float *sub_host, int64_t n,
                           std::vector<float> &cb, hipStream_t s,
                           int seed_off);
@@ -332,7 +350,9 @@ class IVFIndex {
                  std::string *err);
   IndexParams params_;
   bool trained_ = false;
+  /* d_: floats per vector; BINARYIVF: words per vector (bits_ / 32) */
   int d_ = 0, M_ = 0, ksub_ = 256, dsub_ = 0, code_size_ = 0, nlist_ = 0;
+  int bits_ = 0; /* BINARYIVF: dimension in bits */
   int64_t ntotal_ = 0;
   DeviceBuf centroids_, cent_norms_, codebooks_;
   DeviceBuf btable_; /* pct1 B table: nlist x M x ksub f32 */
@@ -574,7 +594,12 @@ class Engine {
   const std::string *field_value(int64_t docid, const std::string &f) const;
   const std::vector<FieldMeta> &scalar_fields() const { return fields_; }
   const std::string &vec_field_name() const { return vec_name_; }
+  /* 4-byte elements per stored vector: the table dimension, except for
+   * BINARYIVF where it is d/32 words (a vector is dimension() * 4 bytes
+   * for every kind) */
   int dimension() const { return dim_; }
+  int table_dimension() const { return table_dim_; }
+  bool binary() const { return params_.kind == IndexKind::BINARYIVF; }
   double last_timing[6] = {0, 0, 0, 0, 0, 0};
   int training_threshold() const { return training_threshold_; }
   std::string status_json() const;
@@ -600,7 +625,8 @@ class Engine {
   std::string path_, log_dir_, space_name_;
   std::string index_type_ = "IVFPQ";
   std::string vec_name_;
-  int dim_ = 0;
+  int dim_ = 0;       /* storage width, see dimension() */
+  int table_dim_ = 0; /* as given to create_table (BINARYIVF: bits) */
   int training_threshold_ = 0;
   std::vector<FieldMeta> fields_;
   std::unordered_map<std::string, StableStrCol> field_vals_;

@@ -52,21 +52,48 @@ int Engine::create_table(const std::string &name,
     if (err) *err = "dimension must be a positive multiple of 4";
     return -1;
   }
+  const bool bin = index_type == "BINARYIVF";
+  if (bin) {
+    /* dimension is in bits (vector_manager.cc:111-115). The reference
+     * takes any multiple of 8; here entries are whole u32 words. */
+    if (dimension % 32 != 0 || dimension < 32 || dimension > 4096) {
+      if (err)
+        *err = "BINARYIVF dimension " + std::to_string(dimension) +
+               " not supported: this engine needs a multiple of 32 bits in "
+               "[32, 4096] (the reference accepts any multiple of 8)";
+      return -1;
+    }
+    if (!extra_vec_fields.empty()) {
+      if (err)
+        *err = "BINARYIVF supports a single (binary) vector field; "
+               "multi-vector tables are not supported with it";
+      return -1;
+    }
+    /* BinaryModelParams defaults (gamma_index_binary_ivf.cc:19-60, :114) */
+    params_.ncentroids = 256;
+    params_.nprobe = 20;
+  }
   space_name_ = space_name_.empty() ? name : space_name_;
   fields_ = scalar_fields;
   for (auto &f : fields_) field_vals_[f.name]; /* default-construct */
   vec_name_ = vec_name;
-  dim_ = dimension;
+  table_dim_ = dimension;
+  dim_ = bin ? dimension / 32 : dimension;
   index_type_ = index_type.empty() ? "IVFPQ" : index_type;
 
   if (params_.parse(index_params_json, err)) return -1;
   if (index_type_ == "IVFPQ") params_.kind = IndexKind::IVFPQ;
   else if (index_type_ == "IVFFLAT") params_.kind = IndexKind::IVFFLAT;
   else if (index_type_ == "FLAT") params_.kind = IndexKind::FLAT;
-  else {
+  else if (bin) {
+    params_.kind = IndexKind::BINARYIVF;
+    /* metric_type, nsubvector, nbits_per_idx, opq: not used by this type */
+    params_.metric_ip = false;
+    params_.has_opq = false;
+  } else {
     if (err)
       *err = "index type " + index_type_ +
-             " not in this build's scope (FLAT/IVFFLAT/IVFPQ)";
+             " not in this build's scope (FLAT/IVFFLAT/IVFPQ/BINARYIVF)";
     return -1;
   }
   if (params_.kind == IndexKind::IVFPQ && params_.nbits == 4 &&
@@ -78,9 +105,24 @@ int Engine::create_table(const std::string &name,
   }
   if (raw_.init(dim_)) return -1;
 
+  /* training_threshold default: max(nlist*39, 256*39) vectors
+   * (ivfpq.cc:137-144 with default_points_per_centroid=39); BINARYIVF:
+   * nlist*39, and buckets start at max(1000, threshold / ncentroids)
+   * entries (gamma_index_binary_ivf.cc:107-110) */
+  if (training_threshold > 0) training_threshold_ = training_threshold;
+  else if (params_.training_threshold > 0)
+    training_threshold_ = params_.training_threshold;
+  else if (bin)
+    training_threshold_ = params_.ncentroids * 39;
+  else
+    training_threshold_ = std::max(params_.ncentroids * 39, 256 * 39);
+  if (bin)
+    params_.bucket_init_size =
+        std::max(1000, training_threshold_ / params_.ncentroids);
+
   if (params_.kind != IndexKind::FLAT) {
     index_ = std::make_unique<IVFIndex>();
-    if (index_->init(dim_, params_)) {
+    if (index_->init(table_dim_, params_)) {
       if (err) *err = "index init failed (check nsubvector divides d, %4)";
       return -1;
     }
@@ -109,13 +151,6 @@ int Engine::create_table(const std::string &name,
     }
     extra_vecs_.push_back(std::move(e));
   }
-  /* training_threshold default: max(nlist*39, 256*39) vectors
-   * (ivfpq.cc:137-144 with default_points_per_centroid=39) */
-  if (training_threshold > 0) training_threshold_ = training_threshold;
-  else if (params_.training_threshold > 0)
-    training_threshold_ = params_.training_threshold;
-  else
-    training_threshold_ = std::max(params_.ncentroids * 39, 256 * 39);
   table_created_ = true;
   return 0;
 }
@@ -140,7 +175,8 @@ int Engine::add_doc(
    * bucket size is published. Anything structural (update of an
    * existing pkey, raw-segment or bucket growth, bitmap growth)
    * retries under the write lock. */
-  if (extra_vecs_.empty()) { /* multi-vector rows take the slow path */
+  /* (BINARYIVF appends always take the write-locked path) */
+  if (extra_vecs_.empty() && !binary()) { /* multi-vector rows: slow path */
     std::shared_lock<std::shared_mutex> g(rw_);
     std::lock_guard<std::mutex> ap(append_mu_);
     int rc = add_doc_fast_(p_key, fields, vec);
@@ -386,7 +422,7 @@ int Engine::rebuild_index(bool drop_before_rebuild, std::string *err) {
     std::unique_lock<std::shared_mutex> g(rw_);
     if (drop_before_rebuild || index_->trained()) {
       index_ = std::make_unique<IVFIndex>();
-      if (index_->init(dim_, params_)) {
+      if (index_->init(table_dim_, params_)) {
         if (err) *err = "index re-init failed";
         return -1;
       }
@@ -719,6 +755,14 @@ int Engine::search(int nq, const float *xq, int k, int nprobe,
   SearchScratch &sc = *scp;
   const int pid = partition_id;
   bool ip = metric == 0 ? params_.metric_ip : (metric == 2);
+  /* BINARYIVF: Hamming distance in the ascending key order; queries are
+   * words, so no norms, no re-rank leg and no l2_sqrt */
+  const bool bin = binary();
+  if (bin) {
+    ip = false;
+    recall_num = 0;
+    l2_sqrt = false;
+  }
   hipStream_t s = sc.stream;
 
   struct Timer {
@@ -764,7 +808,8 @@ int Engine::search(int nq, const float *xq, int k, int nprobe,
     qptr = cached_q_dev_.as<float>();
   }
   if (sc.q_norms.reserve((size_t)nq * 4)) return -1;
-  GAMMA_CHECK(gk::row_norms(s, qptr, nq, dim_, sc.q_norms.as<float>()));
+  if (!bin)
+    GAMMA_CHECK(gk::row_norms(s, qptr, nq, dim_, sc.q_norms.as<float>()));
   if (sc.keys.reserve((size_t)nq * k2 * 8)) return -1;
   if (sc.out_d.reserve((size_t)nq * k * 4)) return -1;
   if (sc.out_i.reserve((size_t)nq * k * 8)) return -1;
@@ -786,7 +831,15 @@ int Engine::search(int nq, const float *xq, int k, int nprobe,
                   !index_ || !index_->trained();
   double t_assign = 0, t_scan = 0;
   bool need_canonical_rerank = true; /* FLAT & IVFFLAT canonicalize */
-  if (use_flat) {
+  if (use_flat && bin) {
+    /* exact Hamming top-k over the raw store: integer distances, so no
+     * margin and no canonical re-rank */
+    GAMMA_CHECK(gk::hamming_flat_scan(
+        s, nq, raw_.size(), dim_, k2, (const uint32_t *)qptr,
+        (const uint32_t *const *)raw_.dev_seg_table(), RawStore::SEG_SHIFT,
+        bm, sc.keys.as<uint64_t>()));
+    need_canonical_rerank = false;
+  } else if (use_flat) {
     /* FLAT margin so GEMM-order rounding cannot evict a true top-k
      * member before the canonical re-rank (DESIGN.md numerics note) */
     int kf = std::min<int64_t>((int64_t)k2 + 64, 1088);
@@ -800,6 +853,9 @@ int Engine::search(int nq, const float *xq, int k, int nprobe,
   } else {
     /* nprobe unset -> the index's configured nprobe (the reference's
      * retrieval-params default, ivfpq.cc:253-294 / ivfpq.h:1049) */
+    /* BINARYIVF: a value outside [1, nlist] falls back to the default
+     * (gamma_index_binary_ivf.cc:299-307) */
+    if (bin && nprobe > index_->params().ncentroids) nprobe = 0;
     if (nprobe <= 0) nprobe = index_->params().nprobe;
     if (nprobe <= 0) nprobe = 80;
     int S = index_->probe_split(nq, k2, nprobe);
@@ -825,7 +881,7 @@ int Engine::search(int nq, const float *xq, int k, int nprobe,
     /* (sub-block partials are unsorted relative to each other, but
      * sort_rows below always sorts — no extra pass needed for S>1) */
     need_canonical_rerank =
-        rerank || params_.kind == IndexKind::IVFFLAT;
+        !bin && (rerank || params_.kind == IndexKind::IVFFLAT);
   }
   tm.rec(2);
   if (KillRegistry::inst().killed(request_id, pid)) return -2;
@@ -1131,7 +1187,7 @@ int Engine::dump_to_(const std::string &dir, std::string *err) {
   wstr(space_name_);
   wstr(index_type_);
   wstr(vec_name_);
-  fwrite(&dim_, 4, 1, f);
+  fwrite(&table_dim_, 4, 1, f);
   fwrite(&training_threshold_, 4, 1, f);
   int64_t maxdoc_now = max_docid_.load(std::memory_order_acquire);
   fwrite(&maxdoc_now, 8, 1, f);
@@ -1209,11 +1265,11 @@ int Engine::load(std::string *err) {
   if (dim <= 0 || dim > (1 << 20) || maxdoc < 0 ||
       maxdoc > ((int64_t)1 << 40))
     return bad("implausible dim/maxdoc");
-  if (table_created_ && dim != dim_) {
+  if (table_created_ && dim != table_dim_) {
     fclose(f);
     if (err)
       *err = "dump dimension " + std::to_string(dim) +
-             " != table dimension " + std::to_string(dim_);
+             " != table dimension " + std::to_string(table_dim_);
     return -1;
   }
   if (table_created_ && idx_type != index_type_) {

@@ -237,4 +237,32 @@ hipError_t flat_stream_scan(hipStream_t s, int nq, int64_t n, int d, int k2,
                             int seg_shift, const uint32_t *bitmap, bool ip,
                             uint64_t *out_keys);
 
+/* ---- BINARYIVF (binary_kernels.hpp). A binary vector of d bits is
+ * W = d/32 u32 words, LSB-first; distances are Hamming distances carried
+ * as exact fp32 in the ordinary ascending (dist, id) key. */
+
+/* out[i*n + j] = (float)popcount(Q_i xor B_j), Q nq x W, B n x W words.
+ * Feeds select_from_dots / argmin_rows with l2 = false, ip_order = false. */
+hipError_t hamming_matrix(hipStream_t s, const uint32_t *Q, int nq,
+                          const uint32_t *B, int64_t n, int W, float *out);
+
+/* Binary IVF fused scan, the contract of ivfpq_scan: one workgroup per
+ * (query, probe-split sub-block), out_keys nq x S x k2 (merge with
+ * sort_rows, ip = false); probes < 0 or >= nlist and empty lists are
+ * skipped; bit 31 of an id and the bitmap drop an entry; kill_flag
+ * (optional) stops the scan. Bucket `data` holds W words per entry,
+ * `svals` is unused. W <= 128, k2 <= 1024. Reads GAMMA_SCAN_BS. */
+hipError_t binivf_scan(hipStream_t s, int nq, int S, int W, int nprobe,
+                       int k2, const uint32_t *queries,
+                       const GammaBucketDev *buckets, int nlist,
+                       const int64_t *probes, const uint32_t *bitmap,
+                       uint64_t *out_keys, const int *kill_flag);
+
+/* Exact Hamming top-k2 over the raw segment table (segments of
+ * 1 << seg_shift vectors of W words), ids = row numbers < n. */
+hipError_t hamming_flat_scan(hipStream_t s, int nq, int64_t n, int W, int k2,
+                             const uint32_t *queries,
+                             const uint32_t *const *segs, int seg_shift,
+                             const uint32_t *bitmap, uint64_t *out_keys);
+
 }  // namespace gk

@@ -2079,3 +2079,6 @@ hipError_t gk::pq_encode_pack4(hipStream_t s, int64_t n, int d, int M,
       n, d, M, x, codebooks, codes);
   return hipGetLastError();
 }
+
+/* BINARYIVF: Hamming matrix, list scan, flat scan */
+#include "binary_kernels.hpp"

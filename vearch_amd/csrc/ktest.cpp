@@ -128,4 +128,27 @@ int GammaKTestIvfpqScan(int nq, int S, int d, int M, int ksub, int nprobe,
                                 qmap));
 }
 
+int GammaKTestHammingMatrix(const uint32_t *Q, int nq, const uint32_t *B,
+                            int64_t n, int W, float *out) {
+  return kt_done(gk::hamming_matrix(nullptr, Q, nq, B, n, W, out));
+}
+
+int GammaKTestBinivfScan(int nq, int S, int W, int nprobe, int k2,
+                         const uint32_t *queries, const void *buckets_dev,
+                         int nlist, const int64_t *probes,
+                         const uint32_t *bitmap, uint64_t *out_keys,
+                         const int *kill_flag) {
+  return kt_done(gk::binivf_scan(nullptr, nq, S, W, nprobe, k2, queries,
+                                 (const GammaBucketDev *)buckets_dev, nlist,
+                                 probes, bitmap, out_keys, kill_flag));
+}
+
+int GammaKTestHammingFlatScan(int nq, int64_t n, int W, int k2,
+                              const uint32_t *queries,
+                              const uint32_t *const *segs, int seg_shift,
+                              const uint32_t *bitmap, uint64_t *out_keys) {
+  return kt_done(gk::hamming_flat_scan(nullptr, nq, n, W, k2, queries, segs,
+                                       seg_shift, bitmap, out_keys));
+}
+
 } /* extern "C" */

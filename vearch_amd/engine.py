@@ -84,6 +84,14 @@ def lib():
                                             c.POINTER(c.c_double)]
         L.GammaCompact.argtypes = [c.c_void_p, c.c_float, i64p]
         L.GammaCompactStats.argtypes = [c.c_void_p, i64p]
+        L.GammaBulkAddBinary.argtypes = [c.c_void_p, c.c_char_p, c.c_int,
+                                         c.c_int, u8p]
+        L.GammaRawSearchBinary.argtypes = [c.c_void_p, c.c_int, u8p,
+                                           c.c_int, c.c_int, c.c_int, f32p,
+                                           i64p]
+        L.GammaDebugCoarseAssignBinary.argtypes = [c.c_void_p, c.c_int, u8p,
+                                                   c.c_int, i64p, f32p]
+        L.GammaDebugGetBinaryCentroids.argtypes = [c.c_void_p, u8p]
         _lib = L
     return _lib
 
@@ -94,6 +102,10 @@ def _fp(a):
 
 def _ip(a):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+
+
+def _bp(a):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
 
 
 def _check(st: CStatus, what):
@@ -113,6 +125,20 @@ class GammaEngine:
             raise RuntimeError("Init failed (GPU required)")
         self.d = 0
         self.vec_name = "emb"
+        self.binary = False
+
+    def _vecs(self, a):
+        """Vectors as the table stores them: float32 (n, d), or for a
+        BINARYIVF table uint8 (n, d/8) with bit i of a vector at
+        (byte[i >> 3] >> (i & 7)) & 1."""
+        if not self.binary:
+            return np.ascontiguousarray(a, dtype=np.float32)
+        a = np.asarray(a)
+        if a.dtype != np.uint8 or a.shape[-1] != self.d // 8:
+            raise ValueError(
+                f"BINARYIVF table takes uint8 arrays of shape (n, "
+                f"{self.d // 8}), got {a.dtype} {a.shape}")
+        return np.ascontiguousarray(a)
 
     def close(self):
         if self.h:
@@ -127,13 +153,21 @@ class GammaEngine:
         from . import fbsenc
         self.d = d
         self.vec_name = vec_name
+        self.binary = index_type == "BINARYIVF"
         buf = fbsenc.build_table(name, list(scalar_fields), vec_name, d,
                                  index_type, index_params,
                                  extra_vecs=extra_vecs)
         _check(lib().CreateTable(self.h, buf, len(buf)), "CreateTable")
 
     def add(self, vecs):
-        vecs = np.ascontiguousarray(vecs, dtype=np.float32)
+        vecs = self._vecs(vecs)
+        if self.binary:
+            rc = lib().GammaBulkAddBinary(self.h, self.vec_name.encode(),
+                                          len(self.vec_name), vecs.shape[0],
+                                          _bp(vecs))
+            if rc != 0:
+                raise RuntimeError(f"GammaBulkAddBinary failed rc={rc}")
+            return
         rc = lib().GammaBulkAdd(self.h, self.vec_name.encode(),
                                 len(self.vec_name), vecs.shape[0],
                                 _fp(vecs))
@@ -144,7 +178,7 @@ class GammaEngine:
         """extra_vecs: [(name, array)] — one entry per extra vector
         field of a multi-vector table."""
         from . import fbsenc
-        vec = np.ascontiguousarray(vec, dtype=np.float32)
+        vec = self._vecs(vec)
         fl = [("_id", p_key.encode(), fbsenc.DATA_STRING)]
         for name, value, dt in fields:
             fl.append((name, value, dt))
@@ -228,13 +262,19 @@ class GammaEngine:
 
     # ---- hot path -------------------------------------------------
     def raw_search(self, queries, k, nprobe=0, rerank=0, metric=0,
-                   request_id=""):
-        q = np.ascontiguousarray(queries, dtype=np.float32)
+                   request_id="", brute=0):
+        """brute: BINARYIVF tables only (exact Hamming scan of the raw
+        store); rerank and metric do not apply to them."""
+        q = self._vecs(queries)
         nq = q.shape[0]
         dists = np.empty((nq, k), dtype=np.float32)
         ids = np.empty((nq, k), dtype=np.int64)
-        rc = lib().GammaRawSearch(self.h, nq, _fp(q), k, nprobe, rerank,
-                                  metric, _fp(dists), _ip(ids))
+        if self.binary:
+            rc = lib().GammaRawSearchBinary(self.h, nq, _bp(q), k, nprobe,
+                                            int(brute), _fp(dists), _ip(ids))
+        else:
+            rc = lib().GammaRawSearch(self.h, nq, _fp(q), k, nprobe, rerank,
+                                      metric, _fp(dists), _ip(ids))
         if rc == -2:
             raise InterruptedError("search killed")
         if rc != 0:
@@ -242,7 +282,7 @@ class GammaEngine:
         return dists, ids
 
     def cache_queries(self, queries):
-        q = np.ascontiguousarray(queries, dtype=np.float32)
+        q = self._vecs(queries)  # binary rows travel as d/32 4-byte words
         rc = lib().GammaCacheQueries(self.h, q.shape[0], _fp(q))
         if rc != 0:
             raise RuntimeError("GammaCacheQueries failed")
@@ -264,13 +304,13 @@ class GammaEngine:
                   min_score=None, max_score=None, l2_sqrt=False,
                   term_filters=(), range_filters=(), operator=0,
                   extra_vec_queries=(), multi_vector_rank=0, ranker="",
-                  offset=0):
+                  offset=0, is_vector_value=False):
         """The real C-ABI Search with protobuf marshalling (reader.go
         path). extra_vec_queries: [(field_name, query_array)] for
         multi-vector search; multi_vector_rank orders by combined
         score; ranker = WeightedRanker JSON."""
         from . import proto
-        q = np.ascontiguousarray(queries, dtype=np.float32)
+        q = self._vecs(queries)
         extra = []
         for ef in extra_vec_queries:
             row = [ef[0],
@@ -285,7 +325,7 @@ class GammaEngine:
             term_filters=term_filters, range_filters=range_filters,
             operator=operator, extra_vec_fields=extra,
             multi_vector_rank=multi_vector_rank, ranker=ranker,
-            offset=offset)
+            offset=offset, is_vector_value=is_vector_value)
         out = ctypes.c_char_p()
         n = ctypes.c_int()
         st = lib().Search(self.h, req, len(req), ctypes.byref(out),
@@ -322,12 +362,16 @@ class GammaEngine:
 
     # ---- debug hooks for parity tests ------------------------------
     def debug_coarse_assign(self, queries, nprobe):
-        q = np.ascontiguousarray(queries, dtype=np.float32)
+        q = self._vecs(queries)
         nq = q.shape[0]
         lists = np.empty((nq, nprobe), dtype=np.int64)
         dists = np.empty((nq, nprobe), dtype=np.float32)
-        rc = lib().GammaDebugCoarseAssign(self.h, nq, _fp(q), nprobe,
-                                          _ip(lists), _fp(dists))
+        if self.binary:
+            rc = lib().GammaDebugCoarseAssignBinary(
+                self.h, nq, _bp(q), nprobe, _ip(lists), _fp(dists))
+        else:
+            rc = lib().GammaDebugCoarseAssign(self.h, nq, _fp(q), nprobe,
+                                              _ip(lists), _fp(dists))
         if rc != 0:
             raise RuntimeError("debug_coarse_assign failed")
         return dists, lists
@@ -341,6 +385,13 @@ class GammaEngine:
         if rc != 0:
             raise RuntimeError("debug_model failed")
         return cent, books
+
+    def debug_binary_centroids(self, nlist):
+        """BINARYIVF: the binarised centroids, uint8 (nlist, d/8)."""
+        cent = np.empty((nlist, self.d // 8), dtype=np.uint8)
+        if lib().GammaDebugGetBinaryCentroids(self.h, _bp(cent)) != 0:
+            raise RuntimeError("debug_binary_centroids failed")
+        return cent
 
     def debug_opq(self, d):
         """d x d OPQ rotation R (row-major, y = R x); raises if none."""

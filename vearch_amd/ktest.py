@@ -50,6 +50,11 @@ def _lib():
         L.GammaKTestIvfpqScan.argtypes = [
             i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp,
             i32, vp, vp, i32, vp, vp, vp]
+        L.GammaKTestHammingMatrix.argtypes = [vp, i32, vp, i64, i32, vp]
+        L.GammaKTestBinivfScan.argtypes = [
+            i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp]
+        L.GammaKTestHammingFlatScan.argtypes = [
+            i32, i64, i32, i32, vp, vp, i32, vp, vp]
         _ready = True
     return L
 
@@ -398,3 +403,85 @@ def ivfpq_scan(lists, probes, probe_dists, queries, centroids, codebooks,
           _p(qm_d, torch.int32))
     od, oi = sort_rows(keys.reshape(nq, S * k2), k2, ip)
     return keys_to_np(keys), od.cpu().numpy(), oi.cpu().numpy()
+
+
+# ------------------------------------------------------------ BINARYIVF
+def _words_dev(bytes_u8):
+    """host uint8 (n, 4*W) -> device int32 (n, W) with the same bytes"""
+    a = np.ascontiguousarray(bytes_u8, dtype=np.uint8)
+    assert a.ndim == 2 and a.shape[1] % 4 == 0
+    return torch.from_numpy(a.view(np.int32).copy()).cuda()
+
+
+def hamming_matrix(Q, B):
+    """gk::hamming_matrix on host uint8 arrays Q (nq, d/8), B (n, d/8),
+    d % 32 == 0 -> float32 (nq, n) numpy."""
+    q_d, b_d = _words_dev(Q), _words_dev(B)
+    nq, W = q_d.shape
+    n = b_d.shape[0]
+    assert b_d.shape[1] == W
+    out = torch.full((nq, n), float("nan"), dtype=torch.float32,
+                     device="cuda")
+    _call("GammaKTestHammingMatrix", _p(q_d, torch.int32), nq,
+          _p(b_d, torch.int32), n, W, _p(out))
+    return out.cpu().numpy()
+
+
+def binivf_scan(lists, probes, queries, S, k2, bitmap=None, kill_flag=False):
+    """One gk::binivf_scan launch on host arrays. lists: one (ids uint32
+    (n,), codes uint8 (n, d/8)) per inverted list (n = 0 is legal), each
+    array in its own device allocation; probes int64 (nq, nprobe) may hold
+    -1 and ids >= nlist; queries uint8 (nq, d/8); bitmap: optional uint32
+    words; kill_flag: pass a device int left at 0 instead of NULL.
+    Returns (keys uint64 (nq, S, k2), dists, ids): the raw partial rows
+    and their gk::sort_rows merge to the top-k2 (-1 / -1 padded; None,
+    None where S * k2 exceeds what sort_rows takes)."""
+    q_d = _words_dev(queries)
+    nq, W = q_d.shape
+    probes = np.ascontiguousarray(probes, dtype=np.int64)
+    nprobe = probes.shape[1]
+    assert probes.shape == (nq, nprobe)
+    pr_d = torch.from_numpy(probes.copy()).cuda()
+    keep, rows = [], []
+    for ids, codes in lists:
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        n = ids.shape[0]
+        codes = np.ascontiguousarray(codes, dtype=np.uint8).reshape(n, 4 * W)
+        t = [torch.from_numpy(ids.view(np.int32).copy()).cuda(),
+             _words_dev(codes)]
+        keep += t
+        rows.append([x.data_ptr() if n else 0 for x in t] + [0, n])
+    bk_d = torch.tensor(rows, dtype=torch.int64).reshape(-1, 4).cuda()
+    bm_d = None if bitmap is None else bitmap_to_dev(bitmap)
+    kf_d = torch.zeros(1, dtype=torch.int32, device="cuda") \
+        if kill_flag else None
+    keys = torch.full((nq, S, k2), 0x5A5A5A5A5A5A5A5A, dtype=torch.int64,
+                      device="cuda")
+    _call("GammaKTestBinivfScan", nq, S, W, nprobe, k2,
+          _p(q_d, torch.int32), _p(bk_d, torch.int64), len(lists),
+          _p(pr_d, torch.int64), _p(bm_d, torch.int32),
+          _p(keys, torch.int64), _p(kf_d, torch.int32))
+    if S * k2 > 2048:  # beyond gk::sort_rows (the engine keeps S*k2 <= 2048)
+        return keys_to_np(keys), None, None
+    od, oi = sort_rows(keys.reshape(nq, S * k2), k2, False)
+    return keys_to_np(keys), od.cpu().numpy(), oi.cpu().numpy()
+
+
+def hamming_flat_scan(queries, base, seg_shift, k2, bitmap=None):
+    """gk::hamming_flat_scan over host uint8 base (n, d/8) split into
+    separately allocated segments of 1 << seg_shift rows; queries uint8
+    (nq, d/8) -> keys uint64 (nq, k2)."""
+    q_d = _words_dev(queries)
+    nq, W = q_d.shape
+    base = np.ascontiguousarray(base, dtype=np.uint8)
+    n = base.shape[0]
+    step = 1 << seg_shift
+    segs = [_words_dev(base[i:i + step]) for i in range(0, n, step)]
+    table = torch.tensor([t.data_ptr() for t in segs],
+                         dtype=torch.int64).cuda()
+    bm_d = None if bitmap is None else bitmap_to_dev(bitmap)
+    out = torch.full((nq, k2), 0x5A5A5A5A5A5A5A5A, dtype=torch.int64,
+                     device="cuda")
+    _call("GammaKTestHammingFlatScan", nq, n, W, k2, _p(q_d, torch.int32),
+          _p(table), seg_shift, _p(bm_d, torch.int32), _p(out))
+    return keys_to_np(out)
