@@ -199,6 +199,25 @@ int GammaKTestHammingFlatScan(int nq, int64_t n, int W, int k2,
                               const uint32_t *const *segs, int seg_shift,
                               const uint32_t *bitmap, uint64_t *out_keys);
 
+/* IVFRABITQ kernels (index_type "IVFRABITQ", nb_bits = 1; d % 32 == 0,
+ * 32 <= d <= 4096). An entry is d/8 + 8 bytes: the sign bits (bit j of a
+ * vector = (byte[j>>3] >> (j&7)) & 1), then the factors A and Mul as
+ * little-endian fp32 — GammaDebugGetList serves the lists in this form,
+ * code_size = d/8 + 8. RabitqEncode: x (n x d), asg (n list numbers; 0 =
+ * every vector in list asg_const), centroids (nlist x d) -> entries
+ * (n x (d/8 + 8) bytes) and svals (n floats, sum of the centroid's
+ * coordinates under the set bits). RabitqScan has GammaKTestIvfpqScan's
+ * bucket / probe / key layout with such entries and svals. */
+int GammaKTestRabitqEncode(int64_t n, int d, const float *x,
+                           const int32_t *asg, int asg_const, int nlist,
+                           const float *centroids, int ip, uint8_t *entries,
+                           float *svals);
+int GammaKTestRabitqScan(int nq, int S, int d, int nprobe, int k2,
+                         const float *queries, const float *centroids,
+                         const void *buckets_dev, int nlist,
+                         const int64_t *probes, const uint32_t *bitmap,
+                         int ip, uint64_t *out_keys, const int *kill_flag);
+
 #ifdef __cplusplus
 }
 #endif

@@ -272,7 +272,15 @@ int IndexParams::parse(const std::string &json, std::string *err) {
   if (v.get_int("ncentroids", x) && x > 0) ncentroids = x;
   if (v.get_int("nsubvector", x) && x > 0) nsubvector = x;
   if (v.get_int("nbits_per_idx", x) && x > 0) nbits = x;
-  if (v.get_int("nprobe", x) && x > 0) nprobe = x;
+  if (v.get_int("nprobe", x) && x > 0) {
+    nprobe = x;
+    nprobe_given = true;
+  }
+  /* IVFRABITQ keys; the range checks run in Engine::create_table, where
+   * the index type is known */
+  if (v.get_int("nb_bits", x)) nb_bits = x == 0 ? -1 : x;
+  if (v.get_int("qb", x)) qb = x;
+  if (v.has("centered")) centered = true;
   if (v.get_int("bucket_init_size", x) && x > 0) bucket_init_size = x;
   if (v.get_int("bucket_max_size", x) && x > 0) bucket_max_size = x;
   if (v.get_int("training_threshold", x) && x > 0) training_threshold = x;
@@ -342,6 +350,13 @@ int IVFIndex::init(int d, const IndexParams &p) {
     if (p.nbits == 4 && p.has_opq) return -1;
     ksub_ = 1 << p.nbits;
     code_size_ = M_ * p.nbits / 8;
+  } else if (params_.kind == IndexKind::IVFRABITQ) {
+    /* whole sign words, and the scan's LDS table bounds d (DESIGN.md
+     * "RaBitQ IVF") */
+    if (d < 32 || d > kRabitqMaxDim || d % 32 != 0) return -1;
+    M_ = 0;
+    dsub_ = 0;
+    code_size_ = d / 8 + 8; /* sign bits, A, Mul */
   } else {
     M_ = 0;
     dsub_ = 0;
@@ -926,7 +941,7 @@ int IVFIndex::add(const float *x_host, const int64_t *vids, int64_t n,
   if (!trained_ || n <= 0) return trained_ ? 0 : -1;
   const int64_t chunk = 65536;
   const size_t entry =
-      params_.kind == IndexKind::IVFPQ ? (size_t)code_size_ : (size_t)d_ * 4;
+      coded() ? (size_t)code_size_ : (size_t)d_ * 4;
 
   DeviceBuf xd, xnorm, dots, asg, resid, codes, sterm;
   std::vector<int32_t> asg_h(std::min(n, chunk));
@@ -977,12 +992,28 @@ int IVFIndex::add(const float *x_host, const int64_t *vids, int64_t n,
       (void)hipMemcpy(sterm_h.data(), sterm.get(), (size_t)cn * 4,
                 hipMemcpyDeviceToHost);
       payload_h = codes_h.data();
+    } else if (rabitq()) {
+      /* sign bits + factors per vector, and its sval, in one launch */
+      if (codes.reserve((size_t)cn * code_size_)) return -1;
+      if (sterm.reserve((size_t)cn * 4)) return -1;
+      if (gk::rabitq_encode(s, cn, d_, xin, asg.as<int32_t>(), 0, nlist_,
+                            centroids_.as<float>(), params_.metric_ip,
+                            codes.as<uint8_t>(),
+                            sterm.as<float>()) != hipSuccess)
+        return -1;
+      codes_h.resize((size_t)cn * code_size_);
+      (void)hipMemcpy(codes_h.data(), codes.get(), (size_t)cn * code_size_,
+                hipMemcpyDeviceToHost);
+      sterm_h.resize(cn);
+      (void)hipMemcpy(sterm_h.data(), sterm.get(), (size_t)cn * 4,
+                hipMemcpyDeviceToHost);
+      payload_h = codes_h.data();
     } else {
       payload_h = (const uint8_t *)(x_host + (size_t)c0 * d_);
     }
 
     /* group by bucket (AddKeys analog, realtime_mem_data.cc) */
-    const bool pq = params_.kind == IndexKind::IVFPQ;
+    const bool pq = coded(); /* code bytes + sval per entry */
     struct Group {
       std::vector<uint32_t> ids;
       std::vector<uint8_t> data;
@@ -1151,6 +1182,19 @@ int IVFIndex::prepare_fast_one(const float *vec_h, hipStream_t s,
                           hipMemcpyDeviceToHost));
     GAMMA_CHECK(hipMemcpy(sval_out, sterm.get(), 4,
                           hipMemcpyDeviceToHost));
+  } else if (rabitq()) {
+    if (codes.reserve((size_t)code_size_)) return -1;
+    if (sterm.reserve(4)) return -1;
+    if (gk::rabitq_encode(s, 1, d_, xin, asg.as<int32_t>(), 0, nlist_,
+                          centroids_.as<float>(), params_.metric_ip,
+                          codes.as<uint8_t>(),
+                          sterm.as<float>()) != hipSuccess)
+      return -1;
+    GAMMA_CHECK(hipStreamSynchronize(s));
+    GAMMA_CHECK(hipMemcpy(code_out, codes.get(), (size_t)code_size_,
+                          hipMemcpyDeviceToHost));
+    GAMMA_CHECK(hipMemcpy(sval_out, sterm.get(), 4,
+                          hipMemcpyDeviceToHost));
   }
   *out_bucket = b;
   return 0;
@@ -1163,11 +1207,9 @@ int IVFIndex::commit_fast_one(int32_t b, int64_t vid, const float *vec_h,
   Bucket &bk = buckets_[b];
   if (bk.size + 1 > bk.cap) return -1; /* prepare checked; appenders
                                           are serialized */
-  const size_t entry = params_.kind == IndexKind::IVFPQ
-                           ? (size_t)code_size_
-                           : (size_t)d_ * 4;
+  const size_t entry = coded() ? (size_t)code_size_ : (size_t)d_ * 4;
   /* data first ... */
-  if (params_.kind == IndexKind::IVFPQ) {
+  if (coded()) {
     GAMMA_CHECK(hipMemcpy((uint8_t *)bk.data->get() +
                               (size_t)bk.size * entry,
                           code, entry, hipMemcpyHostToDevice));
@@ -1232,7 +1274,7 @@ bool IVFIndex::compactable(float min_ratio) const {
 int IVFIndex::compact(float min_ratio, const uint32_t *bitmap_dev,
                       hipStream_t s, CompactStats *st) {
   if (!trained_ || !compactable(min_ratio)) return 0;
-  const bool pq = params_.kind == IndexKind::IVFPQ;
+  const bool pq = coded(); /* code bytes + sval per entry */
   const size_t entry = pq ? (size_t)code_size_ : (size_t)d_ * 4;
   std::vector<int> sel;
   for (int b = 0; b < nlist_; b++)
@@ -1377,7 +1419,7 @@ int IVFIndex::probe_split(int nq, int k2, int nprobe) const {
   /* small batches underfill the 256 CUs with one WG per query: split
    * probes across S sub-workgroups (merged by sort_rows; S*k2 <= 2048
    * keeps the merge a single row sort) */
-  if (params_.kind != IndexKind::IVFPQ && !binary()) return 1;
+  if (!coded() && !binary()) return 1;
   const char *force = getenv("GAMMA_SCAN_S"); /* perf experiments */
   if (force && atoi(force) > 0) {
     int S = atoi(force);
@@ -1486,6 +1528,15 @@ int IVFIndex::search(const float *q_dev, int nq, int k2, int nprobe,
                                sc.probes.as<int64_t>(), bitmap_dev,
                                metric_ip, out_keys_dev, kill_flag_dev,
                                qmap_dev));
+  } else if (rabitq()) {
+    /* the factor A in the entries was encoded for the table's metric; a
+     * request that overrides the metric is served as IVFPQ serves it, in
+     * the requested key order over the codes as they are */
+    GAMMA_CHECK(gk::rabitq_scan(s, nq, S, d_, nprobe, k2, q_dev,
+                                centroids_.as<float>(),
+                                dev_buckets_.as<GammaBucketDev>(), nlist_,
+                                sc.probes.as<int64_t>(), bitmap_dev,
+                                metric_ip, out_keys_dev, kill_flag_dev));
   } else if (binary()) {
     GAMMA_CHECK(gk::binivf_scan(s, nq, S, d_, nprobe, k2,
                                 (const uint32_t *)q_dev,
@@ -1518,7 +1569,7 @@ int IVFIndex::copy_list_to_host(int64_t ln, int64_t *ids, uint8_t *codes,
   if (ln < 0 || ln >= nlist_) return -1;
   const Bucket &bk = buckets_[ln];
   const size_t entry =
-      params_.kind == IndexKind::IVFPQ ? (size_t)code_size_ : (size_t)d_ * 4;
+      coded() ? (size_t)code_size_ : (size_t)d_ * 4;
   if (bk.size == 0) return 0;
   if (ids) {
     std::vector<uint32_t> tmp(bk.size);
@@ -1565,8 +1616,14 @@ int IVFIndex::dump(FILE *f, hipStream_t s) const {
     if (has_opq()) /* write_opq analog (ivfpq.cc:1040) */
       fwrite(opq_R_host_.data(), 4, opq_R_host_.size(), f);
   }
+  if (rabitq()) {
+    /* the factor A depends on the metric: record what the entries were
+     * encoded for, so Load can refuse a table of the other metric */
+    int hdr[2] = {1 /* nb_bits */, params_.metric_ip ? 1 : 0};
+    fwrite(hdr, 4, 2, f);
+  }
   const size_t entry =
-      params_.kind == IndexKind::IVFPQ ? (size_t)code_size_ : (size_t)d_ * 4;
+      coded() ? (size_t)code_size_ : (size_t)d_ * 4;
   fwrite(&ntotal_, 8, 1, f);
   for (int i = 0; i < nlist_; i++) {
     long long sz = buckets_[i].size;
@@ -1584,7 +1641,7 @@ int IVFIndex::dump(FILE *f, hipStream_t s) const {
   return 0;
 }
 
-int IVFIndex::load(FILE *f, hipStream_t s) {
+int IVFIndex::load(FILE *f, hipStream_t s, std::string *err) {
   int tr = 0;
   if (fread(&tr, 4, 1, f) != 1) return -1;
   if (!tr) return 0;
@@ -1620,8 +1677,21 @@ int IVFIndex::load(FILE *f, hipStream_t s) {
                 opq_R_host_.size() * 4, hipMemcpyHostToDevice);
     }
   }
+  if (rabitq()) {
+    int hdr[2] = {0, 0};
+    if (fread(hdr, 4, 2, f) != 2) return -1;
+    if (hdr[0] != 1 || (hdr[1] != 0) != params_.metric_ip) {
+      if (err)
+        *err = std::string("dump IVFRABITQ codes (nb_bits ") +
+               std::to_string(hdr[0]) + ", metric " +
+               (hdr[1] ? "InnerProduct" : "L2") +
+               ") != table (nb_bits 1, metric " +
+               (params_.metric_ip ? "InnerProduct" : "L2") + ")";
+      return -1;
+    }
+  }
   const size_t entry =
-      params_.kind == IndexKind::IVFPQ ? (size_t)code_size_ : (size_t)d_ * 4;
+      coded() ? (size_t)code_size_ : (size_t)d_ * 4;
   if (fread(&ntotal_, 8, 1, f) != 1) return -1;
   for (int i = 0; i < nlist_; i++) {
     long long sz = 0;
@@ -1650,10 +1720,12 @@ int IVFIndex::load(FILE *f, hipStream_t s) {
                 hipMemcpyHostToDevice);
       (void)hipMemcpy(bk.data->get(), data.data(), data.size(),
                 hipMemcpyHostToDevice);
-      if (params_.kind == IndexKind::IVFPQ) {
+      if (coded()) {
         /* S terms are recomputable from codes + the B table, so the
          * dump format is unchanged; allocated here, filled by ONE
-         * pq_sterm_buckets launch after update_dev_buckets below */
+         * pq_sterm_buckets launch after update_dev_buckets below
+         * (IVFRABITQ: svals from sign bits + centroid,
+         * rabitq_sval_buckets) */
         bk.svals = std::make_unique<DeviceBuf>();
         if (bk.svals->reserve((size_t)sz * 4)) return -1;
       }
@@ -1678,6 +1750,12 @@ int IVFIndex::load(FILE *f, hipStream_t s) {
     if (gk::pq_sterm_buckets(s, nlist_, M_, ksub_,
                              dev_buckets_.as<GammaBucketDev>(),
                              btable_.as<float>()) != hipSuccess)
+      return -1;
+    GAMMA_CHECK(hipStreamSynchronize(s));
+  } else if (rabitq()) {
+    if (gk::rabitq_sval_buckets(s, nlist_, d_,
+                                dev_buckets_.as<GammaBucketDev>(),
+                                centroids_.as<float>()) != hipSuccess)
       return -1;
     GAMMA_CHECK(hipStreamSynchronize(s));
   }

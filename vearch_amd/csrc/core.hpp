@@ -198,7 +198,12 @@ class Bitmap {
  * the same float-typed buffers the other kinds use (only copied, never
  * computed on). The vector width the Engine and IVFIndex carry for such a
  * table is therefore W; the bit count is kept next to it. */
-enum class IndexKind { FLAT, IVFPQ, IVFFLAT, BINARYIVF };
+/* IVFRABITQ (gamma_index_ivfrabitq.cc, nb_bits = 1): float vectors like
+ * IVFPQ — raw store, k-means, GEMM coarse assign and the exact re-rank leg
+ * are shared — with list entries of d/8 + 8 code bytes (sign bits, then the
+ * factors A and Mul) plus one device-only sval per entry, the shape of an
+ * IVFPQ entry. See rabitq_kernels.hpp. */
+enum class IndexKind { FLAT, IVFPQ, IVFFLAT, BINARYIVF, IVFRABITQ };
 
 struct IndexParams {
   IndexKind kind = IndexKind::IVFPQ;
@@ -214,6 +219,13 @@ struct IndexParams {
    * OPQMatrix(d, opq_nsubvector, d) at ivfpq.cc:177) */
   bool has_opq = false;
   int opq_nsubvector = 0;
+  /* IVFRABITQ (IVFRABITQModelParams): nb_bits as given, 0 = absent; qb and
+   * centered are range-checked and otherwise unused (every search runs
+   * the unquantized-query estimator). *_given: the key was present. */
+  int nb_bits = 0;
+  int qb = 0;
+  bool centered = false;
+  bool nprobe_given = false;
   /* parse the index-params JSON (ivfpq.h:1065 Parse); empty ok */
   int parse(const std::string &json, std::string *err);
 };
@@ -253,6 +265,15 @@ class IVFIndex {
   int init(int d, const IndexParams &p);
   bool trained() const { return trained_; }
   bool binary() const { return params_.kind == IndexKind::BINARYIVF; }
+  bool rabitq() const { return params_.kind == IndexKind::IVFRABITQ; }
+  /* entries are code_size() code bytes plus one sval (IVFPQ, IVFRABITQ);
+   * the other kinds store the vector itself and no svals */
+  bool coded() const {
+    return params_.kind == IndexKind::IVFPQ || rabitq();
+  }
+  /* IVFRABITQ dimension bound: the scan's LDS holds 20 d bytes of query
+   * table and query next to 25 KB of selector and chunk state */
+  static constexpr int kRabitqMaxDim = 4096;
   /* BINARYIVF: nlist x d/8 bytes of binarised centroids */
   int copy_binary_centroids(uint8_t *out, hipStream_t s) const;
   int train(const float *xt, int64_t n, hipStream_t s, std::string *err);
@@ -323,7 +344,8 @@ class IVFIndex {
   int copy_list_to_host(int64_t ln, int64_t *ids, uint8_t *codes,
                         hipStream_t s) const;
   int dump(FILE *f, hipStream_t s) const;
-  int load(FILE *f, hipStream_t s);
+  /* err (optional): why the index section does not fit this table */
+  int load(FILE *f, hipStream_t s, std::string *err = nullptr);
 
  private:
   int kmeans_gpu(const float *x_host, int64_t n, int dim, int ncl,

@@ -81,6 +81,10 @@ int Engine::create_table(const std::string &name,
   dim_ = bin ? dimension / 32 : dimension;
   index_type_ = index_type.empty() ? "IVFPQ" : index_type;
 
+  /* nothing of a refused earlier attempt carries over into this one */
+  params_.nb_bits = 0;
+  params_.qb = 0;
+  params_.nprobe_given = false;
   if (params_.parse(index_params_json, err)) return -1;
   if (index_type_ == "IVFPQ") params_.kind = IndexKind::IVFPQ;
   else if (index_type_ == "IVFFLAT") params_.kind = IndexKind::IVFFLAT;
@@ -90,10 +94,53 @@ int Engine::create_table(const std::string &name,
     /* metric_type, nsubvector, nbits_per_idx, opq: not used by this type */
     params_.metric_ip = false;
     params_.has_opq = false;
+  } else if (index_type_ == "IVFRABITQ") {
+    /* IVFRABITQModelParams (gamma_index_ivfrabitq.h:337-425). Only the
+     * 1-bit code is built; the reference's default nb_bits is 4, so an
+     * absent value is refused too rather than silently served by a
+     * different index. */
+    params_.kind = IndexKind::IVFRABITQ;
+    params_.has_opq = false;
+    if (params_.nb_bits != 1) {
+      if (err)
+        *err = std::string("IVFRABITQ nb_bits ") +
+               (params_.nb_bits == 0
+                    ? "is absent (the reference default is 4)"
+                    : "= " + std::to_string(std::max(params_.nb_bits, 0))) +
+               ": this engine supports nb_bits: 1 only, and it must be "
+               "given explicitly";
+      return -1;
+    }
+    if (params_.qb < 0 || params_.qb > 8) {
+      if (err)
+        *err = "IVFRABITQ qb = " + std::to_string(params_.qb) +
+               " is out of range: an integer in [0, 8] is required";
+      return -1;
+    }
+    if (dimension % 32 != 0 || dimension < 32 ||
+        dimension > IVFIndex::kRabitqMaxDim) {
+      if (err)
+        *err = "IVFRABITQ dimension " + std::to_string(dimension) +
+               " not supported: this engine needs a multiple of 32 in [32, " +
+               std::to_string(IVFIndex::kRabitqMaxDim) + "]";
+      return -1;
+    }
+    if (params_.nprobe > params_.ncentroids) {
+      if (params_.nprobe_given) {
+        if (err)
+          *err = "IVFRABITQ nprobe = " + std::to_string(params_.nprobe) +
+                 " must not exceed ncentroids = " +
+                 std::to_string(params_.ncentroids);
+        return -1;
+      }
+      params_.nprobe = params_.ncentroids; /* the default 80 on a small
+                                              nlist: probe every list */
+    }
   } else {
     if (err)
       *err = "index type " + index_type_ +
-             " not in this build's scope (FLAT/IVFFLAT/IVFPQ/BINARYIVF)";
+             " not in this build's scope "
+             "(FLAT/IVFFLAT/IVFPQ/BINARYIVF/IVFRABITQ)";
     return -1;
   }
   if (params_.kind == IndexKind::IVFPQ && params_.nbits == 4 &&
@@ -1317,7 +1364,7 @@ int Engine::load(std::string *err) {
   int has_index = 0;
   if (fread(&has_index, 4, 1, f) != 1) return bad("index flag");
   if (has_index && index_) {
-    if (index_->load(f, stream_)) { fclose(f); return -1; }
+    if (index_->load(f, stream_, err)) { fclose(f); return -1; }
     indexed_count_ = index_->ntotal();
   }
   if (ver >= 2) {

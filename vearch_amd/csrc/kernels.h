@@ -265,4 +265,37 @@ hipError_t hamming_flat_scan(hipStream_t s, int nq, int64_t n, int W, int k2,
                              const uint32_t *const *segs, int seg_shift,
                              const uint32_t *bitmap, uint64_t *out_keys);
 
+/* ---- IVFRABITQ (rabitq_kernels.hpp; the maths is at the top of that
+ * file). d % 32 == 0, 32 <= d <= 4096. A bucket entry is d/32 sign words,
+ * then the factors A and Mul as fp32 (d/8 + 8 bytes); bucket `svals` holds
+ * sum_j bit_j * c_j of the entry's list centroid c. */
+
+/* entries[i], svals[i] of vector x_i in list asg[i] (asg null: every
+ * vector in list asg_const; numbers outside [0, nlist) are clamped).
+ * ip selects A = n2 - ||x||^2 instead of n2. Deterministic: fixed
+ * summation order, so equal inputs give equal bytes. */
+hipError_t rabitq_encode(hipStream_t s, int64_t n, int d, const float *x,
+                         const int32_t *asg, int asg_const, int nlist,
+                         const float *centroids, bool ip, uint8_t *entries,
+                         float *svals);
+/* Load path: rebuild every bucket's svals from its entries and centroid
+ * in one launch, bit-identical to rabitq_encode's. */
+hipError_t rabitq_sval_buckets(hipStream_t s, int nlist, int d,
+                               const GammaBucketDev *bks,
+                               const float *centroids);
+/* RaBitQ IVF fused scan, the contract of ivfpq_scan / binivf_scan: one
+ * workgroup per (query, probe-split sub-block), out_keys nq x S x k2
+ * (merge with sort_rows); probes < 0 or >= nlist and empty lists are
+ * skipped; bit 31 of an id and the bitmap drop an entry; kill_flag
+ * (optional) stops the scan. Keys are gamma_make_key<ip> of the estimate
+ * (L2 ascending / inner product descending, ties by id). The kernel builds
+ * its query table and the per-probe scalars itself from queries and
+ * centroids. k2 <= 1024. Reads GAMMA_SCAN_BS; scores do not depend on it
+ * or on S. */
+hipError_t rabitq_scan(hipStream_t s, int nq, int S, int d, int nprobe,
+                       int k2, const float *queries, const float *centroids,
+                       const GammaBucketDev *buckets, int nlist,
+                       const int64_t *probes, const uint32_t *bitmap, bool ip,
+                       uint64_t *out_keys, const int *kill_flag);
+
 }  // namespace gk

@@ -2082,3 +2082,6 @@ hipError_t gk::pq_encode_pack4(hipStream_t s, int64_t n, int d, int M,
 
 /* BINARYIVF: Hamming matrix, list scan, flat scan */
 #include "binary_kernels.hpp"
+
+/* IVFRABITQ: encode, sval rebuild, list scan */
+#include "rabitq_kernels.hpp"

@@ -151,4 +151,24 @@ int GammaKTestHammingFlatScan(int nq, int64_t n, int W, int k2,
                                        seg_shift, bitmap, out_keys));
 }
 
+int GammaKTestRabitqEncode(int64_t n, int d, const float *x,
+                           const int32_t *asg, int asg_const, int nlist,
+                           const float *centroids, int ip, uint8_t *entries,
+                           float *svals) {
+  return kt_done(gk::rabitq_encode(nullptr, n, d, x, asg, asg_const, nlist,
+                                   centroids, ip != 0, entries, svals));
+}
+
+int GammaKTestRabitqScan(int nq, int S, int d, int nprobe, int k2,
+                         const float *queries, const float *centroids,
+                         const void *buckets_dev, int nlist,
+                         const int64_t *probes, const uint32_t *bitmap,
+                         int ip, uint64_t *out_keys, const int *kill_flag) {
+  return kt_done(gk::rabitq_scan(nullptr, nq, S, d, nprobe, k2, queries,
+                                 centroids,
+                                 (const GammaBucketDev *)buckets_dev, nlist,
+                                 probes, bitmap, ip != 0, out_keys,
+                                 kill_flag));
+}
+
 } /* extern "C" */

@@ -410,6 +410,10 @@ class GammaEngine:
         return out
 
     def debug_list(self, list_no, code_size):
+        """(ids int64 with the bit-63 delete mark, codes uint8 (n, code_size))
+        of one inverted list. code_size: nsubvector * nbits / 8 for IVFPQ,
+        d * 4 for IVFFLAT, d / 8 for BINARYIVF, d / 8 + 8 for IVFRABITQ
+        (sign bits, then the factors A and Mul as little-endian fp32)."""
         n = lib().GammaDebugGetList(self.h, list_no, None, None)
         if n < 0:
             raise RuntimeError("debug_list failed")

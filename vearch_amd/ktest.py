@@ -55,6 +55,10 @@ def _lib():
             i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp]
         L.GammaKTestHammingFlatScan.argtypes = [
             i32, i64, i32, i32, vp, vp, i32, vp, vp]
+        L.GammaKTestRabitqEncode.argtypes = [
+            i64, i32, vp, vp, i32, i32, vp, i32, vp, vp]
+        L.GammaKTestRabitqScan.argtypes = [
+            i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp]
         _ready = True
     return L
 
@@ -485,3 +489,72 @@ def hamming_flat_scan(queries, base, seg_shift, k2, bitmap=None):
     _call("GammaKTestHammingFlatScan", nq, n, W, k2, _p(q_d, torch.int32),
           _p(table), seg_shift, _p(bm_d, torch.int32), _p(out))
     return keys_to_np(out)
+
+
+# ------------------------------------------------------------ IVFRABITQ
+def rabitq_encode(x, asg, centroids, ip):
+    """One gk::rabitq_encode launch on host arrays: x float32 (n, d), asg
+    int32 (n,) list numbers, centroids float32 (nlist, d), d % 32 == 0 ->
+    (entries uint8 (n, d/8 + 8), svals float32 (n,)) numpy. Outputs are
+    pre-filled (0xEE / nan) so an unwritten byte is visible."""
+    f32 = lambda a: torch.from_numpy(  # noqa: E731
+        np.ascontiguousarray(a, dtype=np.float32).copy()).cuda()
+    x_d, c_d = f32(x), f32(centroids)
+    n, d = x_d.shape
+    nlist = c_d.shape[0]
+    assert c_d.shape == (nlist, d) and d % 32 == 0
+    a_d = torch.from_numpy(
+        np.ascontiguousarray(asg, dtype=np.int32).copy()).cuda()
+    assert a_d.shape == (n,)
+    ent = torch.full((n, d // 8 + 8), 0xEE, dtype=torch.uint8, device="cuda")
+    sv = torch.full((n,), float("nan"), dtype=torch.float32, device="cuda")
+    _call("GammaKTestRabitqEncode", n, d, _p(x_d), _p(a_d, torch.int32), 0,
+          nlist, _p(c_d), int(bool(ip)), _p(ent), _p(sv))
+    return ent.cpu().numpy(), sv.cpu().numpy()
+
+
+def rabitq_scan(lists, probes, queries, centroids, S, k2, ip, bitmap=None,
+                kill_flag=False):
+    """One gk::rabitq_scan launch on host arrays. lists: one (ids uint32
+    (n,), entries uint8 (n, d/8 + 8), svals float32 (n,)) per inverted list
+    (n = 0 is legal), each array in its own device allocation; probes int64
+    (nq, nprobe) may hold -1 and ids >= nlist; queries float32 (nq, d);
+    centroids float32 (nlist, d); bitmap: optional uint32 words; kill_flag:
+    pass a device int left at 0 instead of NULL.
+    Returns (keys uint64 (nq, S, k2), scores, ids): the raw partial rows
+    and their gk::sort_rows merge to the top-k2 (-1 / -1 padded)."""
+    f32 = lambda a: torch.from_numpy(  # noqa: E731
+        np.ascontiguousarray(a, dtype=np.float32).copy()).cuda()
+    q_d, c_d = f32(queries), f32(centroids)
+    nq, d = q_d.shape
+    nlist = len(lists)
+    assert c_d.shape == (nlist, d) and d % 32 == 0
+    assert S * k2 <= 2048
+    cs = d // 8 + 8
+    probes = np.ascontiguousarray(probes, dtype=np.int64)
+    nprobe = probes.shape[1]
+    assert probes.shape == (nq, nprobe)
+    pr_d = torch.from_numpy(probes.copy()).cuda()
+    keep, rows = [], []
+    for ids, ent, svals in lists:
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        n = ids.shape[0]
+        ent = np.ascontiguousarray(ent, dtype=np.uint8).reshape(n, cs)
+        svals = np.ascontiguousarray(svals, dtype=np.float32)
+        assert svals.shape == (n,)
+        t = [torch.from_numpy(ids.view(np.int32).copy()).cuda(),
+             _words_dev(ent), torch.from_numpy(svals.copy()).cuda()]
+        keep += t
+        rows.append([x.data_ptr() if n else 0 for x in t] + [n])
+    bk_d = torch.tensor(rows, dtype=torch.int64).reshape(-1, 4).cuda()
+    bm_d = None if bitmap is None else bitmap_to_dev(bitmap)
+    kf_d = torch.zeros(1, dtype=torch.int32, device="cuda") \
+        if kill_flag else None
+    keys = torch.full((nq, S, k2), 0x5A5A5A5A5A5A5A5A, dtype=torch.int64,
+                      device="cuda")
+    _call("GammaKTestRabitqScan", nq, S, d, nprobe, k2, _p(q_d), _p(c_d),
+          _p(bk_d, torch.int64), nlist, _p(pr_d, torch.int64),
+          _p(bm_d, torch.int32), int(bool(ip)), _p(keys, torch.int64),
+          _p(kf_d, torch.int32))
+    od, oi = sort_rows(keys.reshape(nq, S * k2), k2, ip)
+    return keys_to_np(keys), od.cpu().numpy(), oi.cpu().numpy()
