@@ -182,6 +182,16 @@ int GammaKTestIvfpqScan(int nq, int S, int d, int M, int ksub, int nprobe,
                         const int64_t *probes, const uint32_t *bitmap, int ip,
                         uint64_t *out_keys, const int *kill_flag,
                         const int32_t *qmap);
+/* The sliced-table scan (k_ivfpq_scan_wide, kernels.h "Wide tables") reads
+ * atab for both metrics: PqTablesIp is gk::pq_tables_ip, the inner-product
+ * table (nq x M x 256). IvfpqWideInfo: out5 = {sub-quantizers per table
+ * slice, entries per tile at the current GAMMA_SCAN_BS, 1 if a launch of
+ * this (d, M, ksub, k2) takes the sliced kernel else 0, 1 if an L2 launch
+ * reads atab (what the engine builds a table for), the same for inner
+ * product}. */
+int GammaKTestPqTablesIp(int nq, int d, int M, const float *queries,
+                         const float *codebooks, float *out);
+int GammaKTestIvfpqWideInfo(int d, int M, int ksub, int k2, int *out5);
 
 /* BINARYIVF kernels (W = d/32 u32 words per vector, LSB-first bits):
  * HammingMatrix out[i*n+j] = popcount(Q_i xor B_j) as f32; BinivfScan has

@@ -322,7 +322,7 @@ int IndexParams::parse(const std::string &json, std::string *err) {
 }
 
 /* ---------------------------------------------------------------- IVFIndex */
-int IVFIndex::init(int d, const IndexParams &p) {
+int IVFIndex::init(int d, const IndexParams &p, std::string *err) {
   params_ = p;
   d_ = d;
   if (p.has_opq) {
@@ -350,6 +350,19 @@ int IVFIndex::init(int d, const IndexParams &p) {
     if (p.nbits == 4 && p.has_opq) return -1;
     ksub_ = 1 << p.nbits;
     code_size_ = M_ * p.nbits / 8;
+    /* the scan kernels' LDS: nothing legal here may fail at search */
+    if (!gk::ivfpq_scan_fits(d, M_, ksub_)) {
+      if (err)
+        *err = p.nbits == 8
+                   ? "IVFPQ: dimension " + std::to_string(d) +
+                         " exceeds the scan's bound of " +
+                         std::to_string((int)gk::IVFPQ_MAX_DIM)
+                   : "IVFPQ nbits_per_idx=4: 64*nsubvector + 4*dimension = " +
+                         std::to_string(64 * (long long)M_ + 4ll * d) +
+                         " exceeds the scan's bound of " +
+                         std::to_string((int)gk::IVFPQ4_MAX_LDS_TERM);
+      return -1;
+    }
   } else if (params_.kind == IndexKind::IVFRABITQ) {
     /* whole sign words, and the scan's LDS table bounds d (DESIGN.md
      * "RaBitQ IVF") */
@@ -1472,14 +1485,18 @@ int IVFIndex::search(const float *q_dev, int nq, int k2, int nprobe,
     /* the 8-bit fast scan builds its L2 query table in LDS from
      * codebooks_ + cwn_; only the generic and 4-bit kernels still read a
      * precomputed A table */
-    const float *atab = nullptr;
-    if (!metric_ip && !gk::ivfpq_scan_builds_table(M_, ksub_, k2)) {
-      if (sc.atab.reserve((size_t)nq * M_ * ksub_ * 4)) return -1;
-      GAMMA_CHECK(gk::pq_tables_a(s, nq, d_, M_, ksub_, q_dev,
-                                  codebooks_.as<float>(),
-                                  sc.atab.as<float>()));
-      atab = sc.atab.as<float>();
-    }
+    const bool reads_tab =
+        gk::ivfpq_scan_reads_table(d_, M_, ksub_, k2, metric_ip);
+    /* A precomputed query table is M*ksub floats per query (384 KB at
+     * M = 384): table build and scan run over groups of queries so that
+     * this scratch stays within kScanTableCapBytes. A group is a row
+     * range of every per-query array, so results and the (nq, S, k2)
+     * layout do not change. */
+    const size_t tab_row = (size_t)M_ * ksub_ * 4;
+    int gq = nq;
+    if (reads_tab && (size_t)nq * tab_row > kScanTableCapBytes)
+      gq = (int)std::max<size_t>(1, kScanTableCapBytes / tab_row);
+    if (reads_tab && sc.atab.reserve((size_t)gq * tab_row)) return -1;
     /* cache-clustered schedule (opt-in): sort the batch by first
      * probed list so workgroups touching the same lists run together
      * while those lists are L2/LLC-resident. MEASURED NEUTRAL on the
@@ -1489,7 +1506,7 @@ int IVFIndex::search(const float *q_dev, int nq, int k2, int nprobe,
      * stream sync only adds cost. Kept behind GAMMA_QSORT=1 for
      * workloads with heavier list skew. */
     const int32_t *qmap_dev = nullptr;
-    if (nq >= 2048 && getenv("GAMMA_QSORT") != nullptr) {
+    if (nq >= 2048 && gq == nq && getenv("GAMMA_QSORT") != nullptr) {
       if (sc.qcol.reserve((size_t)nq * 4)) return -1;
       if (sc.qmap.reserve((size_t)nq * 4)) return -1;
       GAMMA_CHECK(gk::extract_probe0(s, nq, nprobe,
@@ -1520,14 +1537,30 @@ int IVFIndex::search(const float *q_dev, int nq, int k2, int nprobe,
                                  s));
       qmap_dev = sc.qmap.as<int32_t>();
     }
-    GAMMA_CHECK(gk::ivfpq_scan(s, nq, S, d_, M_, ksub_, nprobe, k2, q_dev,
-                               centroids_.as<float>(),
-                               codebooks_.as<float>(), atab,
-                               cwn_.as<float>(), sc.pdists.as<float>(),
-                               dev_buckets_.as<GammaBucketDev>(), nlist_,
-                               sc.probes.as<int64_t>(), bitmap_dev,
-                               metric_ip, out_keys_dev, kill_flag_dev,
-                               qmap_dev));
+    for (int g0 = 0; g0 < nq; g0 += gq) {
+      const int gn = std::min(gq, nq - g0);
+      const float *qg = q_dev + (size_t)g0 * d_;
+      const float *atab = nullptr;
+      if (reads_tab) {
+        if (metric_ip)
+          GAMMA_CHECK(gk::pq_tables_ip(s, gn, d_, M_, qg,
+                                       codebooks_.as<float>(),
+                                       sc.atab.as<float>()));
+        else
+          GAMMA_CHECK(gk::pq_tables_a(s, gn, d_, M_, ksub_, qg,
+                                      codebooks_.as<float>(),
+                                      sc.atab.as<float>()));
+        atab = sc.atab.as<float>();
+      }
+      GAMMA_CHECK(gk::ivfpq_scan(
+          s, gn, S, d_, M_, ksub_, nprobe, k2, qg, centroids_.as<float>(),
+          codebooks_.as<float>(), atab, cwn_.as<float>(),
+          sc.pdists.as<float>() + (size_t)g0 * nprobe,
+          dev_buckets_.as<GammaBucketDev>(), nlist_,
+          sc.probes.as<int64_t>() + (size_t)g0 * nprobe, bitmap_dev,
+          metric_ip, out_keys_dev + (size_t)g0 * S * k2, kill_flag_dev,
+          qmap_dev));
+    }
   } else if (rabitq()) {
     /* the factor A in the entries was encoded for the table's metric; a
      * request that overrides the metric is served as IVFPQ serves it, in

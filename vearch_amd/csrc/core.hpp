@@ -262,7 +262,8 @@ struct SearchScratch {
 class IVFIndex {
  public:
   /* d: vector dimension (BINARYIVF: in bits, a multiple of 32) */
-  int init(int d, const IndexParams &p);
+  /* err: filled where a shape is refused for a named bound */
+  int init(int d, const IndexParams &p, std::string *err = nullptr);
   bool trained() const { return trained_; }
   bool binary() const { return params_.kind == IndexKind::BINARYIVF; }
   bool rabitq() const { return params_.kind == IndexKind::IVFRABITQ; }
@@ -274,6 +275,10 @@ class IVFIndex {
   /* IVFRABITQ dimension bound: the scan's LDS holds 20 d bytes of query
    * table and query next to 25 KB of selector and chunk state */
   static constexpr int kRabitqMaxDim = 4096;
+  /* IVFPQ: cap on the per-search query-table scratch (SearchScratch::atab,
+   * nsubvector KB per query at 8 bits); search() walks larger batches in
+   * query groups (DESIGN.md "Wide PQ") */
+  static constexpr size_t kScanTableCapBytes = (size_t)512 << 20;
   /* BINARYIVF: nlist x d/8 bytes of binarised centroids */
   int copy_binary_centroids(uint8_t *out, hipStream_t s) const;
   int train(const float *xt, int64_t n, hipStream_t s, std::string *err);

@@ -169,8 +169,12 @@ int Engine::create_table(const std::string &name,
 
   if (params_.kind != IndexKind::FLAT) {
     index_ = std::make_unique<IVFIndex>();
-    if (index_->init(table_dim_, params_)) {
-      if (err) *err = "index init failed (check nsubvector divides d, %4)";
+    std::string ierr;
+    if (index_->init(table_dim_, params_, &ierr)) {
+      if (err)
+        *err = ierr.empty()
+                   ? "index init failed (check nsubvector divides d, %4)"
+                   : ierr;
       return -1;
     }
   }
@@ -191,8 +195,11 @@ int Engine::create_table(const std::string &name,
       IndexParams pe = params_;
       if (pe.nsubvector && e->dim % pe.nsubvector) pe.nsubvector = 0;
       e->index = std::make_unique<IVFIndex>();
-      if (e->index->init(e->dim, pe)) {
-        if (err) *err = "extra vector index init failed for " + ev.first;
+      std::string ierr;
+      if (e->index->init(e->dim, pe, &ierr)) {
+        if (err)
+          *err = "extra vector index init failed for " + ev.first +
+                 (ierr.empty() ? "" : ": " + ierr);
         return -1;
       }
     }
@@ -298,11 +305,17 @@ int Engine::add_doc_fast_(
   if (raw_.would_grow(1)) return 1;
   if (!bitmap_.has_capacity(docid + 1)) return 1;
   int32_t bucket = -1;
-  uint8_t code[256];
+  uint8_t code_small[256];
+  std::vector<uint8_t> code_big; /* PQ entries above 256 bytes */
+  uint8_t *code = code_small;
   float sval = 0.0f;
   bool commit_index = false;
   if (index_ && index_->trained()) {
-    if (index_->code_size() > (int)sizeof(code)) return 1;
+    if (index_->code_size() > (int)sizeof(code_small)) {
+      if (!index_->coded()) return 1;
+      code_big.resize((size_t)index_->code_size());
+      code = code_big.data();
+    }
     int rc = index_->prepare_fast_one(vec, stream_, &bucket, code, &sval);
     if (rc != 0) return rc; /* 1 = bucket needs extension -> slow */
     commit_index = true;

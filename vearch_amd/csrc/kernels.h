@@ -168,13 +168,36 @@ hipError_t pq_sterm_buckets(hipStream_t s, int nlist, int M, int ksub,
 /* L2 table source: when ivfpq_scan_builds_table(M, ksub, k2) the kernel
  * (8-bit codes, M in {16,32,64,96}, k2 + block size within the selector
  * cap) builds the query table itself from codebooks + cwn (pq_cwn) and
- * atab may be null; otherwise atab (pq_tables_a) is required and cwn may
- * be null. Inner product needs neither. Both functions read the same
- * launch knobs: GAMMA_SCAN_BS (256|512 threads; default 512) and
+ * atab may be null (unless the launch is wide, below); otherwise atab
+ * (pq_tables_a) is required and cwn may be null. Inner product needs
+ * neither. Both functions read the same launch knobs: GAMMA_SCAN_BS (256|512 threads; default 512) and
  * GAMMA_ADC_C (1|2 codes staged per thread, 4-bit kernel only — the
  * 8-bit fast path accepts and ignores it). Results do not depend on
  * either knob. */
+/* Wide tables: where k_ivfpq_scan's resident table (M KB of LDS) cannot
+ * launch — ivfpq_scan_is_wide(d, M, ksub, k2); M >= 144 always, M of 136
+ * to 140 depending on k2 and d — 8-bit codes run k_ivfpq_scan_wide, which
+ * keeps IVFPQ_WIDE_MS sub-quantizers of the table in LDS at a time and
+ * walks tiles of ivfpq_wide_tile() entries. It reads the query table from
+ * `atab` for BOTH metrics: pq_tables_a for L2, pq_tables_ip for inner
+ * product (nq x M x 256 floats; the caller bounds nq per launch).
+ * GAMMA_SCAN_WIDE=1, read per launch, forces it at any M. Keys do not
+ * depend on which kernel ran. */
+enum { IVFPQ_WIDE_MS = 32, IVFPQ_WIDE_E = 4 };
+int ivfpq_wide_tile(); /* entries per tile at the current GAMMA_SCAN_BS */
+bool ivfpq_scan_is_wide(int d, int M, int ksub, int k2);
+/* whether a table of this shape can be scanned at every legal k2, for
+ * both metrics (the LDS bound on d, and on M for 4-bit codes) */
+enum { IVFPQ_MAX_DIM = 16384, IVFPQ4_MAX_LDS_TERM = 131072 };
+bool ivfpq_scan_fits(int d, int M, int ksub);
+hipError_t pq_tables_ip(hipStream_t s, int nq, int d, int M,
+                        const float *queries, const float *codebooks,
+                        float *out);
 bool ivfpq_scan_builds_table(int M, int ksub, int k2);
+/* whether this launch reads `atab`, i.e. what the caller has to build:
+ * every wide launch (both metrics, any M — a fast-path M is wide too once
+ * 4*d fills the LDS), and L2 launches whose kernel builds no table */
+bool ivfpq_scan_reads_table(int d, int M, int ksub, int k2, bool ip);
 hipError_t ivfpq_scan(hipStream_t s, int nq, int S, int d, int M, int ksub,
                       int nprobe,
                       int k2, const float *queries, const float *centroids,

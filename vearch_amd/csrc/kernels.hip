@@ -896,6 +896,329 @@ k_ivfpq_scan(int nq, int S, int d, int M, int nprobe, int k2,
     out_keys[((int64_t)q * S + sub) * k2 + i] = res[i];
 }
 
+/* --------------------------------- IVFPQ fused scan, 8-bit, sliced table
+ * k_ivfpq_scan keeps all M*256 table floats in LDS, which stops fitting at
+ * M ~ 140. This kernel serves any M with LDS that does not grow with M: it
+ * holds GAMMA_WIDE_MS sub-quantizers of the table at a time.
+ *
+ * Same contract and the same flat, chunked probe walk as the fast path
+ * above. A chunk's flat space is cut into tiles of T = BS*GAMMA_WIDE_E
+ * entries; thread tid owns entries tile*T + e*BS + tid, e < E, and keeps
+ * their running distances in registers (compile-time indexed only). Per
+ * tile the slice loop is the outer loop: load the slice's code words of
+ * the E entries, barrier, copy the slice's rows of the query table
+ * (`tab`, nq x M x 256 floats: gk::pq_tables_a for L2, gk::pq_tables_ip
+ * for IP — a slice is one contiguous run of it) into LDS, barrier, add.
+ * Slices ascend and m ascends inside a slice, so every distance is the
+ * add chain of k_ivfpq_scan, bit for bit; the last slice may be partial.
+ * Entries are M bytes, M % 4 == 0: code loads are 16 bytes wide where M
+ * and every list of the chunk allow it, single dwords otherwise. The adds
+ * run word by word across the E entries (E independent chains).
+ * After the last slice the E entries are pushed in rounds of two entries
+ * per thread (margin 2*BS; one entry and margin BS where k2 + 2*BS exceeds
+ * the selector cap), each followed by the selector's flush check.
+ * The kill flag is polled once per chunk and once per tile by thread 0;
+ * the block reads the answer from LDS behind the next barrier. */
+#define GAMMA_WIDE_MS 32 /* sub-quantizers per table slice: 32 KB of LDS */
+#define GAMMA_WIDE_E 4   /* entries per thread per tile */
+
+static size_t gamma_wide_qs_off(int k2) {
+  size_t o = (size_t)GAMMA_WIDE_MS * 256 * 4 +
+             ((size_t)GAMMA_SORT_CAP + k2) * 8;
+  return (o + 15) / 16 * 16;
+}
+static size_t gamma_wide_chunk_off(int k2, int d, bool ip) {
+  return (gamma_wide_qs_off(k2) + (ip ? (size_t)d * 4 : 0) + 7) / 8 * 8;
+}
+static size_t gamma_wide_smem(int k2, int d, bool ip) {
+  return gamma_wide_chunk_off(k2, d, ip) + sizeof(GammaScanChunk);
+}
+
+typedef uint32_t gamma_u32x4 __attribute__((ext_vector_type(4)));
+typedef const __attribute__((address_space(1))) gamma_u32x4 *gamma_gu128p;
+
+/* one entry's code words of one slice: 16-byte loads for a whole slice of
+ * 16-byte-aligned entries, single words otherwise. A partial slice has
+ * msw < MSW words; the words past it repeat its last word (never read
+ * past the entry) and are not used. */
+template <int MSW, bool A16>
+__device__ __forceinline__ void gamma_wide_load(uint32_t (&w)[MSW],
+                                                gamma_gu32p p, int msw) {
+  if (A16) {
+    gamma_gu128p p4 = (gamma_gu128p)p;
+#pragma unroll
+    for (int u = 0; u < MSW / 4; u++) {
+      const gamma_u32x4 v = p4[u];
+      w[4 * u] = v.x; w[4 * u + 1] = v.y;
+      w[4 * u + 2] = v.z; w[4 * u + 3] = v.w;
+    }
+  } else {
+#pragma unroll
+    for (int u = 0; u < MSW; u++) w[u] = p[min(u, msw - 1)];
+  }
+}
+
+/* acc += row[m][code_m] for the four sub-quantizers of one code word,
+ * ascending m; row = the table row of the word's first sub-quantizer */
+__device__ __forceinline__ float gamma_wide_add4(float acc, const float *row,
+                                                 uint32_t wv) {
+  acc += row[wv & 255u];
+  acc += row[256 + ((wv >> 8) & 255u)];
+  acc += row[512 + ((wv >> 16) & 255u)];
+  acc += row[768 + (wv >> 24)];
+  return acc;
+}
+
+/* two 512-thread workgroups per CU are 4 waves per SIMD (<= 128 VGPRs);
+ * three 256-thread ones are 3 */
+template <bool IP, int BS>
+__global__ void __launch_bounds__(BS, BS == 512 ? 4 : 3)
+k_ivfpq_scan_wide(int nq, int S, int d, int M, int nprobe, int k2,
+                  const float *__restrict__ queries,
+                  const float *__restrict__ centroids,
+                  const float *__restrict__ tab,
+                  const float *__restrict__ probe_dists,
+                  const GammaBucketDev *__restrict__ buckets, int nlist,
+                  const int64_t *__restrict__ probes,
+                  const uint32_t *__restrict__ bitmap,
+                  uint64_t *__restrict__ out_keys,
+                  const int *__restrict__ kill_flag,
+                  const int32_t *__restrict__ qmap) {
+  extern __shared__ char smem[];
+  constexpr int MS = GAMMA_WIDE_MS, E = GAMMA_WIDE_E, MSW = MS / 4;
+  constexpr unsigned T = (unsigned)BS * E;
+  constexpr int NT = MS * 256 / 4 / BS; /* table float4s per thread */
+  float *lut = (float *)smem;                       /* MS*256 */
+  uint64_t *sortbuf = (uint64_t *)(smem + (size_t)MS * 256 * 4);
+  uint64_t *res = sortbuf + GAMMA_SORT_CAP;
+  const size_t qs_off =
+      ((size_t)MS * 256 * 4 + ((size_t)GAMMA_SORT_CAP + k2) * 8 + 15) / 16 *
+      16;
+  float *qs = (float *)(smem + qs_off);             /* d, IP only */
+  GammaScanChunk *ch = (GammaScanChunk *)(
+      smem + (qs_off + (IP ? (size_t)d * 4 : 0) + 7) / 8 * 8);
+
+  const int bq = blockIdx.x / S;
+  const int sub = blockIdx.x - bq * S;
+  if (bq >= nq) return;
+  const int q = qmap ? qmap[bq] : bq;
+  if (IP) {
+    const float *qg = queries + (int64_t)q * d;
+    for (int i = threadIdx.x; i < d; i += blockDim.x) qs[i] = qg[i];
+  }
+  const float *qtab = tab + (size_t)q * M * 256;
+
+  GammaSelector sel;
+  sel.init(sortbuf, res, ch->state, k2);  /* has the barrier qs needs */
+
+  const unsigned tid = threadIdx.x;
+  const int nslice = (M + MS - 1) / MS;
+  const int np_sub = sub < nprobe ? (nprobe - sub + S - 1) / S : 0;
+  bool killed = false;
+  for (int c0 = 0; c0 < np_sub && !killed;) {
+    const int cn = min(GAMMA_SCAN_PCH, np_sub - c0);
+    int misaligned = 0;
+    if ((int)tid < cn) { /* one thread per probe of the chunk */
+      const int p = sub + (c0 + (int)tid) * S;
+      int64_t ln = probes[(int64_t)q * nprobe + p];
+      GammaBucketDev bk;
+      bk.ids = nullptr; bk.data = nullptr; bk.svals = nullptr;
+      bk.size = 0;
+      float dis0 = 0.0f;
+      if (ln >= 0 && ln < nlist) {
+        bk = buckets[ln];
+        if (IP) { /* dis0 = dot(q, c), canonical serial order */
+          const float *cent = centroids + (size_t)ln * d;
+          for (int e = 0; e < d; e++) dis0 = fmaf(qs[e], cent[e], dis0);
+        } else {
+          dis0 = probe_dists[(int64_t)q * nprobe + p];
+        }
+      }
+      long long sz = bk.size < 0 ? 0 : bk.size;
+      if (sz > 0x7fffffffll) sz = 0x7fffffffll; /* ids are 31-bit */
+      ch->ids[tid] = (gamma_gu32p)bk.ids;
+      ch->codes[tid] = (gamma_gu8p)bk.data;
+      ch->svals[tid] = (gamma_gf32p)bk.svals;
+      ch->dis0[tid] = dis0;
+      ch->sz[tid] = (int)sz;
+      misaligned = sz > 0 && ((uintptr_t)bk.data & 15) != 0;
+    }
+    if (tid == 0) {
+      ch->kill[0] = kill_flag
+                        ? __hip_atomic_load(kill_flag, __ATOMIC_RELAXED,
+                                            __HIP_MEMORY_SCOPE_AGENT)
+                        : 0;
+      ch->ncons = cn;
+      ch->off[0] = 0;
+    }
+    /* barrier + vote: 16-byte code loads need every list of the chunk
+     * 16-byte aligned (and M % 16 == 0) */
+    const bool a16 = !__syncthreads_or(misaligned) && (M & 15) == 0;
+    if ((int)tid < cn) {
+      long long cum = 0;
+      for (int u = 0; u <= (int)tid; u++) cum += ch->sz[u];
+      if (cum > 0x7fffffffll) { /* flat space is 31-bit: end the chunk
+                                   before this probe (never the first) */
+        atomicMin(&ch->ncons, (int)tid);
+        cum = 0x7fffffffll;
+      }
+      ch->off[tid + 1] = (int)cum;
+    }
+    __syncthreads();
+    killed = ch->kill[0] != 0;
+    const int ncons = ch->ncons;
+    const unsigned total = killed ? 0u : (unsigned)ch->off[ncons];
+    const unsigned ntile = (total + T - 1) / T;
+    c0 += ncons;
+
+    /* this thread's current list: entries [lstart, lend). Its flat
+     * indices ascend over (tile, e), so the walk only moves forward. */
+    int li = 0;
+    unsigned lstart = 0, lend = (unsigned)ch->off[1];
+    gamma_gu32p pid = ch->ids[0];
+    gamma_gu8p pcodes = ch->codes[0];
+    gamma_gf32p psv = ch->svals[0];
+    float ldis0 = ch->dis0[0];
+
+    for (unsigned tile = 0; tile < ntile; tile++) {
+      /* Nothing is read past a list's size: a slot with no entry (only
+       * in a chunk's last tile) aliases the chunk's last entry and
+       * carries the skip bit. */
+      gamma_gu32p cw[E];
+      uint32_t id[E];
+      float dis[E];
+#pragma unroll
+      for (int e = 0; e < E; e++) {
+        const unsigned g0 = tile * T + (unsigned)e * BS + tid;
+        const bool live = g0 < total;
+        const unsigned g = live ? g0 : total - 1;
+        if (g >= lend) { /* LDS only */
+          do {
+            li++;
+            lend = (unsigned)ch->off[li + 1];
+          } while (g >= lend);
+          lstart = (unsigned)ch->off[li];
+          pid = ch->ids[li];
+          pcodes = ch->codes[li];
+          psv = ch->svals[li];
+          ldis0 = ch->dis0[li];
+        }
+        const unsigned j = g - lstart;
+        uint32_t idv = pid[j];
+        if (!live ||
+            (!(idv >> 31) && gamma_bitmap_test(bitmap, (uint64_t)idv)))
+          idv |= 0x80000000u;
+        id[e] = idv;
+        dis[e] = IP ? ldis0 : ldis0 + psv[j];
+        cw[e] = (gamma_gu32p)(pcodes + (size_t)j * M);
+      }
+      if (tid == 0) /* this tile's poll; read behind the slice barrier */
+        ch->kill[1] = kill_flag
+                          ? __hip_atomic_load(kill_flag, __ATOMIC_RELAXED,
+                                              __HIP_MEMORY_SCOPE_AGENT)
+                          : 0;
+      for (int sl = 0; sl < nslice; sl++) {
+        const int msw = min(MSW, (M - sl * MS) >> 2); /* words this slice */
+        /* the slice's code words are requested in front of the barrier */
+        uint32_t w[E][MSW];
+        if (a16 && msw == MSW) {
+#pragma unroll
+          for (int e = 0; e < E; e++)
+            gamma_wide_load<MSW, true>(w[e], cw[e] + sl * MSW, msw);
+        } else {
+#pragma unroll
+          for (int e = 0; e < E; e++)
+            gamma_wide_load<MSW, false>(w[e], cw[e] + sl * MSW, msw);
+        }
+        __syncthreads(); /* the previous slice's gather is done */
+        if (sl == 0 && (killed = ch->kill[1] != 0)) break;
+        {
+          const float4 *src =
+              (const float4 *)(qtab + (size_t)sl * MS * 256);
+          const int n4 = msw * 256; /* float4s of the slice */
+#pragma unroll
+          for (int k = 0; k < NT; k++) {
+            const int i = (int)tid + k * BS;
+            if (i < n4) ((float4 *)lut)[i] = src[i];
+          }
+        }
+        __syncthreads();
+        /* word by word across the E entries: E independent add chains
+         * with 4*E lookups in flight. The scheduling fence keeps the
+         * compiler from hoisting a whole slice's lookups into registers
+         * (which spills at 128 VGPRs). */
+#pragma unroll
+        for (int u = 0; u < MSW; u++) {
+          if (u < msw) { /* uniform */
+#pragma unroll
+            for (int e = 0; e < E; e++)
+              dis[e] = gamma_wide_add4(dis[e], lut + u * 1024, w[e][u]);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      if (killed) break; /* uniform: every thread read the same slot */
+      /* Push rounds: two entries per thread and margin 2*BS where that
+       * fits the selector cap, else one and margin BS. A push may follow
+       * a flush check only behind another barrier: a wave still reading
+       * the append counter for its check must not see a later push, or
+       * the block would disagree on flushing. The last check of a tile is
+       * followed by the next tile's slice barriers (or the chunk's). */
+      auto push = [&](int e) {
+        if (!(id[e] >> 31)) sel.push(gamma_make_key<IP>(dis[e], id[e]));
+      };
+      if (k2 + 2 * BS <= GAMMA_SORT_CAP) {
+        static_assert(GAMMA_WIDE_E == 4, "two rounds of two entries");
+        push(0); push(1);
+        sel.maybe_flush(2 * BS);
+        __syncthreads();
+        push(2); push(3);
+        sel.maybe_flush(2 * BS);
+      } else {
+#pragma unroll
+        for (int e = 0; e < E; e++) {
+          push(e);
+          sel.maybe_flush(BS);
+          if (e + 1 < E) __syncthreads();
+        }
+      }
+    }
+    /* barrier: the chunk is rewritten next round */
+    __syncthreads();
+  }
+  sel.finish();
+  for (int i = threadIdx.x; i < k2; i += blockDim.x)
+    out_keys[((int64_t)q * S + sub) * k2 + i] = res[i];
+}
+
+/* the IP query table of the sliced scan: out[q][m][j] = q_m . cw_mj in the
+ * serial fmaf chain k_ivfpq_scan runs for its own IP table */
+__global__ void k_pq_iptable(int64_t total, int d, int M,
+                             const float *__restrict__ queries,
+                             const float *__restrict__ codebooks,
+                             float *__restrict__ out) {
+  int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= total) return;
+  const int dsub = d / M;
+  const int64_t q = e / ((int64_t)M * 256);
+  const int mj = (int)(e - q * M * 256); /* m*256 + j */
+  const float *cw = codebooks + (size_t)mj * dsub;
+  const float *qm = queries + q * d + (mj >> 8) * dsub;
+  float acc = 0.0f;
+  for (int t = 0; t < dsub; t++) acc = fmaf(qm[t], cw[t], acc);
+  out[e] = acc;
+}
+
+hipError_t gk::pq_tables_ip(hipStream_t s, int nq, int d, int M,
+                            const float *queries, const float *codebooks,
+                            float *out) {
+  const int64_t total = (int64_t)nq * M * 256;
+  if (total <= 0) return hipSuccess;
+  k_pq_iptable<<<dim3((uint32_t)((total + WG - 1) / WG)), dim3(WG), 0, s>>>(
+      total, d, M, queries, codebooks, out);
+  return hipGetLastError();
+}
+
 /* ------------------------------------------- IVFPQ fused scan, 4-bit codes
  * Same contract as k_ivfpq_scan for nbits_per_idx=4 (ksub=16). Entries
  * are M/2 bytes: byte b holds sub-quantizer 2b in bits 0-3 and 2b+1 in
@@ -1163,8 +1486,40 @@ static bool gamma_scan8_fast(int M, int k2, int BS) {
   return k2 + BS <= GAMMA_SORT_CAP && gamma_scan_fast_m(M);
 }
 
+/* GAMMA_SCAN_WIDE=1 sends every 8-bit launch to k_ivfpq_scan_wide (tests
+ * and tools/wide_probe.py); unset, only launches whose resident table
+ * does not fit LDS go there */
+static bool gamma_scan_force_wide() {
+  const char *e = getenv("GAMMA_SCAN_WIDE");
+  return e && atoi(e) == 1;
+}
+static_assert(GAMMA_WIDE_MS == gk::IVFPQ_WIDE_MS &&
+                  GAMMA_WIDE_E == gk::IVFPQ_WIDE_E,
+              "kernels.h exports the wide scan's slice and tile factors");
+
+int gk::ivfpq_wide_tile() { return gamma_scan_bs() * GAMMA_WIDE_E; }
+
+bool gk::ivfpq_scan_is_wide(int d, int M, int ksub, int k2) {
+  return ksub == 256 && (gamma_scan_force_wide() ||
+                         gamma_scan8_smem(M, k2, d) > 160 * 1024);
+}
+
+bool gk::ivfpq_scan_fits(int d, int M, int ksub) {
+  if (ksub == 256) /* wide kernel, inner product, largest k2 */
+    return d <= IVFPQ_MAX_DIM &&
+           gamma_wide_smem(GAMMA_SEL_MAX_K, d, true) <= 160 * 1024;
+  /* k_ivfpq_scan4: table + query; selector scratch and state on top */
+  return (size_t)M * 64 + (size_t)d * 4 <= IVFPQ4_MAX_LDS_TERM;
+}
+
 bool gk::ivfpq_scan_builds_table(int M, int ksub, int k2) {
-  return ksub == 256 && gamma_scan8_fast(M, k2, gamma_scan_bs());
+  return ksub == 256 && !gamma_scan_force_wide() &&
+         gamma_scan8_fast(M, k2, gamma_scan_bs());
+}
+
+bool gk::ivfpq_scan_reads_table(int d, int M, int ksub, int k2, bool ip) {
+  return gk::ivfpq_scan_is_wide(d, M, ksub, k2) ||
+         (!ip && !gk::ivfpq_scan_builds_table(M, ksub, k2));
 }
 
 hipError_t gk::ivfpq_scan(hipStream_t s, int nq, int S, int d, int M,
@@ -1180,6 +1535,28 @@ hipError_t gk::ivfpq_scan(hipStream_t s, int nq, int S, int d, int M,
   if (ksub != 256 && ksub != 16) return hipErrorInvalidValue;
   const int BS = gamma_scan_bs();
   dim3 g((uint32_t)nq * (uint32_t)S);
+  if (ksub == 256 && gk::ivfpq_scan_is_wide(d, M, ksub, k2)) {
+    /* sliced table: LDS does not grow with M. The push rounds need
+     * k2 + block size within the selector cap. */
+    if (!atab || M <= 0 || (M & 3)) return hipErrorInvalidValue;
+    const int WBS = k2 + BS <= GAMMA_SORT_CAP ? BS : 256;
+    if (k2 + WBS > GAMMA_SORT_CAP) return hipErrorInvalidValue;
+    const size_t smem = gamma_wide_smem(k2, d, ip);
+    if (smem > 160 * 1024) return hipErrorInvalidValue;
+#define GAMMA_LAUNCH_WIDE(IPV, BSV)                                       \
+  k_ivfpq_scan_wide<IPV, BSV><<<g, dim3(BSV), smem, s>>>(                 \
+      nq, S, d, M, nprobe, k2, queries, centroids, atab, probe_dists,     \
+      buckets, nlist, probes, bitmap, out_keys, kill_flag, qmap)
+    if (ip) {
+      if (WBS == 256) GAMMA_LAUNCH_WIDE(true, 256);
+      else GAMMA_LAUNCH_WIDE(true, 512);
+    } else {
+      if (WBS == 256) GAMMA_LAUNCH_WIDE(false, 256);
+      else GAMMA_LAUNCH_WIDE(false, 512);
+    }
+#undef GAMMA_LAUNCH_WIDE
+    return hipGetLastError();
+  }
   if (ksub == 256) {
     const bool fast = gamma_scan8_fast(M, k2, BS);
     if (!ip && (fast ? !cwn : !atab)) return hipErrorInvalidValue;

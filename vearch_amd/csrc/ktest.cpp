@@ -128,6 +128,20 @@ int GammaKTestIvfpqScan(int nq, int S, int d, int M, int ksub, int nprobe,
                                 qmap));
 }
 
+int GammaKTestPqTablesIp(int nq, int d, int M, const float *queries,
+                         const float *codebooks, float *out) {
+  return kt_done(gk::pq_tables_ip(nullptr, nq, d, M, queries, codebooks, out));
+}
+
+int GammaKTestIvfpqWideInfo(int d, int M, int ksub, int k2, int *out5) {
+  out5[0] = gk::IVFPQ_WIDE_MS;
+  out5[1] = gk::ivfpq_wide_tile();
+  out5[2] = gk::ivfpq_scan_is_wide(d, M, ksub, k2) ? 1 : 0;
+  out5[3] = gk::ivfpq_scan_reads_table(d, M, ksub, k2, false) ? 1 : 0;
+  out5[4] = gk::ivfpq_scan_reads_table(d, M, ksub, k2, true) ? 1 : 0;
+  return 0;
+}
+
 int GammaKTestHammingMatrix(const uint32_t *Q, int nq, const uint32_t *B,
                             int64_t n, int W, float *out) {
   return kt_done(gk::hamming_matrix(nullptr, Q, nq, B, n, W, out));

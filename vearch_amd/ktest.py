@@ -50,6 +50,9 @@ def _lib():
         L.GammaKTestIvfpqScan.argtypes = [
             i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp,
             i32, vp, vp, i32, vp, vp, vp]
+        L.GammaKTestPqTablesIp.argtypes = [i32, i32, i32, vp, vp, vp]
+        L.GammaKTestIvfpqWideInfo.argtypes = [
+            i32, i32, i32, i32, c.POINTER(c.c_int)]
         L.GammaKTestHammingMatrix.argtypes = [vp, i32, vp, i64, i32, vp]
         L.GammaKTestBinivfScan.argtypes = [
             i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp]
@@ -351,19 +354,65 @@ def pq_lut_l2(queries, codebooks, M, ksub):
     return out
 
 
+def pq_tables_ip(queries, codebooks, M):
+    """gk::pq_tables_ip: the inner-product query table the sliced-table
+    scan reads, (nq, M, 256) f32."""
+    assert queries.is_contiguous() and codebooks.is_contiguous()
+    nq, d = queries.shape
+    assert d % M == 0 and codebooks.numel() == 256 * d
+    out = torch.full((nq, M, 256), float("nan"), dtype=torch.float32,
+                     device=queries.device)
+    _call("GammaKTestPqTablesIp", nq, d, M, _p(queries, torch.float32),
+          _p(codebooks, torch.float32), _p(out))
+    return out
+
+
+WIDE_MS = 32  # IVFPQ_WIDE_MS of kernels.h: sub-quantizers per table slice
+WIDE_E = 4    # IVFPQ_WIDE_E: entries per thread per tile
+
+
+def ivfpq_wide_info(d, M, k2, ksub=256):
+    """(slice, tile, is_wide) of the sliced-table scan as the library
+    reports them under the current launch knobs: sub-quantizers per table
+    slice, entries per tile (WIDE_E x the GAMMA_SCAN_BS block size), and
+    whether a launch of this shape takes k_ivfpq_scan_wide."""
+    return _wide_info(d, M, k2, ksub)[:3]
+
+
+def _wide_info(d, M, k2, ksub):
+    out = (ctypes.c_int * 5)()
+    rc = _lib().GammaKTestIvfpqWideInfo(d, M, ksub, k2, out)
+    if rc != 0:
+        raise KTestError("GammaKTestIvfpqWideInfo", rc)
+    return (int(out[0]), int(out[1]), bool(out[2]), bool(out[3]),
+            bool(out[4]))
+
+
+def ivfpq_scan_reads_table(d, M, k2, ip, ksub=256):
+    """gk::ivfpq_scan_reads_table: whether a launch of this shape reads
+    `atab` -- the decision IVFIndex::search builds its query table by."""
+    return _wide_info(d, M, k2, ksub)[4 if ip else 3]
+
+
 def ivfpq_scan(lists, probes, probe_dists, queries, centroids, codebooks,
-               S, k2, ip, bitmap=None, qmap=None):
+               S, k2, ip, bitmap=None, qmap=None, kill_flag=None,
+               code_offsets=None):
     """One gk::ivfpq_scan launch (8-bit codes) on host arrays.
     lists: one (ids uint32 (n,), codes uint8 (n, M), svals float32 (n,))
     per inverted list, n = that list's size (0 is legal); every array gets
     its own device allocation. probes int64 (nq, nprobe) may hold -1 and
     ids >= nlist; probe_dists float32 (nq, nprobe). queries (nq, d),
     centroids (nlist, d), codebooks (M, 256, d/M). bitmap: optional uint32
-    words; qmap: optional int32 (nq,) query schedule.
+    words; qmap: optional int32 (nq,) query schedule. kill_flag: None
+    passes NULL; an int passes a device int holding that value (1 = a
+    flag raised before the launch). code_offsets: optional {list index:
+    byte offset (a multiple of 4)}: that list's codes start this far into
+    their allocation, so they are 4-byte but not 16-byte aligned.
     Returns (keys, dists, ids): keys uint64 (nq, S, k2) as the kernel
     wrote them, and the merge the engine applies to the S partial rows of
     a query (gk::sort_rows over S*k2 keys), top-k2: dists float32 and ids
-    int64 (nq, k2), -1 / -1 where fewer than k2 candidates exist."""
+    int64 (nq, k2), -1 / -1 where fewer than k2 candidates exist (None,
+    None where S * k2 exceeds what sort_rows takes)."""
     f32 = lambda a: torch.from_numpy(  # noqa: E731
         np.ascontiguousarray(a, dtype=np.float32).copy()).cuda()
     q_d, cent_d, cb_d = f32(queries), f32(centroids), f32(codebooks)
@@ -379,16 +428,20 @@ def ivfpq_scan(lists, probes, probe_dists, queries, centroids, codebooks,
     pd_d = f32(probe_dists)
     assert pd_d.shape == (nq, nprobe)
     keep, rows = [], []
-    for ids, codes, svals in lists:
+    for li, (ids, codes, svals) in enumerate(lists):
         ids = np.ascontiguousarray(ids, dtype=np.uint32)
         n = ids.shape[0]
         codes = np.ascontiguousarray(codes, dtype=np.uint8).reshape(n, M)
         svals = np.ascontiguousarray(svals, dtype=np.float32)
         assert svals.shape == (n,)
+        off = (code_offsets or {}).get(li, 0)
+        assert off % 4 == 0 and off >= 0
+        buf = np.full(off + n * M, 0xEE, dtype=np.uint8)
+        buf[off:] = codes.ravel()
+        cbuf = torch.from_numpy(buf).cuda()
         t = [torch.from_numpy(ids.view(np.int32).copy()).cuda(),
-             torch.from_numpy(codes.copy()).cuda(),
-             torch.from_numpy(svals.copy()).cuda()]
-        keep += t
+             cbuf[off:], torch.from_numpy(svals.copy()).cuda()]
+        keep += t + [cbuf]
         rows.append([x.data_ptr() if n else 0 for x in t] + [n])
     bk_d = torch.tensor(rows, dtype=torch.int64).reshape(-1, 4).cuda()
     bm_d = None if bitmap is None else bitmap_to_dev(bitmap)
@@ -396,15 +449,22 @@ def ivfpq_scan(lists, probes, probe_dists, queries, centroids, codebooks,
     if qmap is not None:
         qm_d = torch.from_numpy(
             np.ascontiguousarray(qmap, dtype=np.int32).copy()).cuda()
-    atab = None if ip else pq_tables_a(q_d, cb_d, M, 256)
+    # the resident-table kernels build their own IP table and ignore atab;
+    # the sliced-table kernel reads it for both metrics
+    atab = pq_tables_ip(q_d, cb_d, M) if ip \
+        else pq_tables_a(q_d, cb_d, M, 256)
     cwn = pq_cwn(cb_d, M, 256)
+    kf_d = None if kill_flag is None else torch.full(
+        (1,), int(kill_flag), dtype=torch.int32, device="cuda")
     keys = torch.full((nq, S, k2), 0x5A5A5A5A5A5A5A5A, dtype=torch.int64,
                       device="cuda")
     _call("GammaKTestIvfpqScan", nq, S, d, M, 256, nprobe, k2, _p(q_d),
           _p(cent_d), _p(cb_d), _p(atab), _p(cwn), _p(pd_d),
           _p(bk_d, torch.int64), nlist, _p(pr_d, torch.int64),
-          _p(bm_d, torch.int32), int(bool(ip)), _p(keys, torch.int64), None,
-          _p(qm_d, torch.int32))
+          _p(bm_d, torch.int32), int(bool(ip)), _p(keys, torch.int64),
+          _p(kf_d, torch.int32), _p(qm_d, torch.int32))
+    if S * k2 > 2048:  # beyond gk::sort_rows (the engine keeps S*k2 <= 2048)
+        return keys_to_np(keys), None, None
     od, oi = sort_rows(keys.reshape(nq, S * k2), k2, ip)
     return keys_to_np(keys), od.cpu().numpy(), oi.cpu().numpy()
 
