@@ -154,6 +154,33 @@ def test_kernel_binivf_scan_bs256(W, monkeypatch):
     _run_scan_modes(W, k2s=(10, 1024), Ss=(1, 4))
 
 
+def test_kernel_binivf_scan_kill_flag():
+    """A flag raised before the launch is read at the first chunk close:
+    the launch returns and every row is EMPTY. A flag left at 0 changes
+    nothing. The W = 1 case with its probe rows repeated five times: 40
+    probes, two chunks at S = 1. k2 = 1024 is the largest the launcher
+    takes, and k2 + 2 * 512 = 2048 still fits the selector, so this kernel
+    only ever checks every second pass; a k2 above that bound cannot be
+    launched."""
+    from vearch_amd import ktest
+    ids, codes, queries, probes = _scan_case(1, 201)
+    probes = np.tile(probes, 5)
+    assert probes.shape[1] > 32
+    lists = list(zip(ids, codes))
+    no_marks = [np.zeros(n, dtype=bool) for n in SIZES]
+    for S, k2 in ((1, 10), (2, 1024)):
+        keys, _, oi = ktest.binivf_scan(lists, probes, queries, S, k2,
+                                        kill_flag=1)
+        assert keys.shape == (NQ_SCAN, S, k2)
+        assert np.all(keys == np.uint64(kr.EMPTY)), (S, k2)
+        assert np.all(oi == -1)
+        keys, _, _ = ktest.binivf_scan(lists, probes, queries, S, k2,
+                                       kill_flag=0)
+        want = _expected_partials(ids, codes, queries, probes, S, k2,
+                                  no_marks, None)
+        assert np.array_equal(keys, want), (S, k2)
+
+
 # --------------------------------------------------------- hamming_flat_scan
 @pytest.mark.parametrize("W", [1, 2, 3, 8])
 def test_kernel_hamming_flat_scan(W):

@@ -203,6 +203,32 @@ def test_kernel_scan_dyadic_bs256(D, monkeypatch):
                (1, 1, True, "none")], 700 + D)
 
 
+def test_kernel_scan_kill_flag():
+    """A flag raised before the launch is read at the first chunk close:
+    the launch returns and every row is EMPTY. A flag left at 0 changes
+    nothing. The D = 32 dyadic case: 46 probes, two chunks at S = 1.
+    k2 = 1024 is the largest the launcher takes, and k2 + 2 * 512 = 2048
+    still fits the selector, so this kernel only ever checks every second
+    pass; a k2 above that bound cannot be launched."""
+    from vearch_amd import ktest
+    sizes = BS_SIZES + [3 + (i % 5) for i in range(34)]
+    combos = ((1, 10), (2, 1024))
+    cent, ids, vecs, queries, probes = _scan_case(32, 532, True, sizes,
+                                                  int(sum(sizes)) + 64)
+    assert probes.shape[1] > 32
+    for ip in (False, True):
+        dev = [(i, c, s) for i, (c, s) in zip(ids, _encode_lists(cent, vecs,
+                                                                 ip))]
+        for S, k2 in combos:
+            keys, _, oi = ktest.rabitq_scan(dev, probes, queries, cent, S, k2,
+                                            ip, kill_flag=1)
+            assert keys.shape == (NQ_SCAN, S, k2)
+            assert np.all(keys == np.uint64(kr.EMPTY)), (ip, S, k2)
+            assert np.all(oi == -1)
+    _run_scan(32, True, sizes, 2.0 ** -20,
+              [(S, k2, 0, "none") for S, k2 in combos], 532)
+
+
 @pytest.mark.parametrize("D", [64, 128])
 def test_kernel_scan_gaussian(D):
     """Gaussian inputs: sums round, so the bound is rabitq_ref.tol,

@@ -132,7 +132,7 @@ class Case:
             rows.append(row)
         return np.stack(rows)
 
-    def run(self, name, S, k2, bitmap=False, qmap=None):
+    def run(self, name, S, k2, bitmap=False, qmap=None, kill_flag=None):
         from vearch_amd import ktest
         t = self.tables[name]
         nq = t.shape[0]
@@ -140,7 +140,7 @@ class Case:
             self.lists, t, self.probe_dists[name], self.queries[:nq],
             self.centroids, self.codebooks, S, k2, self.ip,
             bitmap=kr.bitmap_words(self.deleted) if bitmap else None,
-            qmap=qmap)
+            qmap=qmap, kill_flag=kill_flag)
 
 
 _cases = {}
@@ -205,6 +205,20 @@ def test_scan_large_k2_checks_every_pass(ip):
     c = _case(128, 32, ip)
     _check(c, "rows8", 1, 1030)
     _check(c, "2chunk+3", 1, 1030)
+
+
+@pytest.mark.parametrize("ip", [False, True], ids=["l2", "ip"])
+def test_scan_kill_flag(ip):
+    """A flag raised before the launch is read at the first chunk close:
+    the launch returns and every row is EMPTY. A flag left at 0 changes
+    nothing."""
+    c = _case(32, 16, ip)
+    for S, k2 in ((1, 10), (2, 1024)):
+        keys, _, ids = c.run("2chunk+3", S, k2, kill_flag=1)
+        assert keys.shape == (2, S, k2)
+        assert (keys == kr._EMPTY).all(), (S, k2)
+        assert (ids == -1).all()
+        _check(c, "2chunk+3", S, k2, kill_flag=0)
 
 
 def test_scan_adc_c_knob_is_inert(monkeypatch):

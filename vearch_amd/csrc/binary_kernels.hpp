@@ -1,8 +1,7 @@
 /*
  * binary_kernels.hpp — Hamming-distance kernels of the BINARYIVF index
  * (gamma_index_binary_ivf.cc). Included at the end of kernels.hip: it
- * uses that file's WG, GammaScanChunk, the global-address-space pointer
- * typedefs and the GAMMA_SCAN_BS launch knob.
+ * uses that file's WG and GAMMA_SCAN_BS launch knob, and scan_walk.hpp.
  *
  * A binary vector of d bits is W = d/32 little-endian u32 words (bit i of
  * the vector is bit i&31 of word i>>5, i.e. LSB-first inside each byte).
@@ -100,21 +99,15 @@ hipError_t gk::hamming_matrix(hipStream_t s, const uint32_t *Q, int nq,
 }
 
 /* ------------------------------------------------- binary IVF fused scan
- * Same contract and the same flat, chunked walk as k_ivfpq_scan's fast
- * path: a workgroup serves (query, probe-split sub-block), takes its
- * probes in chunks of <= GAMMA_SCAN_PCH lists whose entries form one flat
- * index space (prefix sums in LDS), and thread tid handles flat entry
- * it*BS + tid, so the trip count is uniform and each pass pushes at most
- * one key per thread.
+ * Same contract as k_ivfpq_scan's fast path and the same chunked probe
+ * walk (scan_walk.hpp): a workgroup serves (query, probe-split sub-block).
  *
  * U = words per load unit (4/2/1, the widest that divides W). NU > 0:
  * the entry is NU units held in registers, the query words live in
- * registers too, and the loads of pass it+1 (id + entry) are issued into
- * a second register set before pass it is counted — in straight-line
- * code: a lane with no entry left re-reads the chunk's last entry and is
- * marked dead. NU == 0: entry length is a runtime count of units; the id
- * is prefetched the same way and the entry is streamed unit by unit
- * against the query words in LDS (same-address reads, broadcast). */
+ * registers too, and a pass prefetches id + entry. NU == 0: entry length
+ * is a runtime count of units; only the id is prefetched and the entry is
+ * streamed unit by unit against the query words in LDS (same-address
+ * reads, broadcast). */
 template <int U, int NU>
 struct GammaBinElem {
   uint32_t w[NU ? U * NU : 1];
@@ -123,10 +116,11 @@ struct GammaBinElem {
   bool live;
 };
 
-static size_t gamma_binscan_qs_off(int k2) {
+/* dynamic LDS of k_binivf_scan: selector scratch + result, query, chunk */
+__host__ __device__ static size_t gamma_binscan_qs_off(int k2) {
   return ((size_t)GAMMA_SORT_CAP + k2) * 8;
 }
-static size_t gamma_binscan_chunk_off(int k2, int W) {
+__host__ __device__ static size_t gamma_binscan_chunk_off(int k2, int W) {
   return (gamma_binscan_qs_off(k2) + (size_t)W * 4 + 7) / 8 * 8;
 }
 
@@ -142,9 +136,9 @@ k_binivf_scan(int nq, int S, int W, int nprobe, int k2,
   extern __shared__ char smem[];
   uint64_t *sortbuf = (uint64_t *)smem;
   uint64_t *res = sortbuf + GAMMA_SORT_CAP;
-  uint32_t *qs = (uint32_t *)(res + k2); /* W */
-  GammaScanChunk *ch = (GammaScanChunk *)(
-      smem + ((((size_t)GAMMA_SORT_CAP + k2) * 8 + (size_t)W * 4 + 7) / 8 * 8));
+  uint32_t *qs = (uint32_t *)(smem + gamma_binscan_qs_off(k2)); /* W */
+  GammaScanChunk *ch =
+      (GammaScanChunk *)(smem + gamma_binscan_chunk_off(k2, W));
 
   const int q = blockIdx.x / S;
   const int sub = blockIdx.x - q * S;
@@ -165,70 +159,30 @@ k_binivf_scan(int nq, int S, int W, int nprobe, int k2,
 
   const unsigned tid = threadIdx.x;
   const int np_sub = sub < nprobe ? (nprobe - sub + S - 1) / S : 0;
+  const int *kf = kill_flag ? kill_flag : (const int *)probes;
   bool killed = false;
   for (int c0 = 0; c0 < np_sub && !killed;) {
     const int cn = min(GAMMA_SCAN_PCH, np_sub - c0);
     if ((int)tid < cn) { /* one thread per probe of the chunk */
       const int p = sub + (c0 + (int)tid) * S;
-      int64_t ln = probes[(int64_t)q * nprobe + p];
-      GammaBucketDev bk;
-      bk.ids = nullptr; bk.data = nullptr; bk.svals = nullptr;
-      bk.size = 0;
+      const int64_t ln = probes[(int64_t)q * nprobe + p];
+      GammaBucketDev bk = gamma_null_bucket();
       if (ln >= 0 && ln < nlist) bk = buckets[ln];
-      long long sz = bk.size < 0 ? 0 : bk.size;
-      if (sz > 0x7fffffffll) sz = 0x7fffffffll; /* ids are 31-bit */
-      ch->ids[tid] = (gamma_gu32p)bk.ids;
-      ch->codes[tid] = (gamma_gu8p)bk.data;
-      ch->sz[tid] = (int)sz;
+      gamma_chunk_put<false>(ch, tid, bk);
     }
-    if (tid == 0) {
-      /* in-flight kill: agent-scope load, one thread polls and the block
-       * reads its answer from LDS behind the barrier */
-      ch->kill[0] = kill_flag
-                        ? __hip_atomic_load(kill_flag, __ATOMIC_RELAXED,
-                                            __HIP_MEMORY_SCOPE_AGENT)
-                        : 0;
-      ch->ncons = cn;
-      ch->off[0] = 0;
-    }
-    __syncthreads();
-    if ((int)tid < cn) {
-      long long cum = 0;
-      for (int u = 0; u <= (int)tid; u++) cum += ch->sz[u];
-      if (cum > 0x7fffffffll) { /* flat space is 31-bit: end the chunk
-                                   before this probe (never the first) */
-        atomicMin(&ch->ncons, (int)tid);
-        cum = 0x7fffffffll;
-      }
-      ch->off[tid + 1] = (int)cum;
-    }
-    __syncthreads();
-    killed = ch->kill[0] != 0;
-    const int ncons = ch->ncons;
-    const unsigned total = killed ? 0u : (unsigned)ch->off[ncons];
-    const unsigned niter = (total + BS - 1) / BS;
-    c0 += ncons;
+    const GammaChunkSpan sp = gamma_chunk_close(ch, cn, kill_flag);
+    c0 += sp.ncons;
 
-    /* this thread's current list: entries [lstart, lend) */
-    int li = 0;
-    unsigned lstart = 0, lend = (unsigned)ch->off[1];
+    GammaListCursor cur;
+    cur.reset(ch, sp.total);
     gamma_gu32p pid = ch->ids[0];
     gamma_gu32p pcodes = (gamma_gu32p)ch->codes[0];
 
     auto fetch = [&](GammaBinElem<U, NU> &e, unsigned it) {
-      const unsigned g0 = it * BS + tid;
-      e.live = g0 < total;
-      const unsigned g = e.live ? g0 : total - 1;
-      if (g >= lend) { /* LDS only */
-        do {
-          li++;
-          lend = (unsigned)ch->off[li + 1];
-        } while (g >= lend);
-        lstart = (unsigned)ch->off[li];
+      const unsigned j = cur.seek(ch, it * BS + tid, e.live, [&](int li) {
         pid = ch->ids[li];
         pcodes = (gamma_gu32p)ch->codes[li];
-      }
-      const unsigned j = g - lstart;
+      });
       e.id = pid[j];
       e.cw = pcodes + (size_t)j * W;
       if constexpr (NU > 0) {
@@ -241,8 +195,6 @@ k_binivf_scan(int nq, int S, int W, int nprobe, int k2,
         }
       }
     };
-    /* name an entry's registers so its loads are retired by one counted
-     * wait and none stays pending into the next prefetch */
     auto retire = [&](const GammaBinElem<U, NU> &e) {
       if constexpr (NU > 0) {
 #pragma unroll
@@ -263,22 +215,18 @@ k_binivf_scan(int nq, int S, int W, int nprobe, int k2,
           !gamma_bitmap_test(bitmap, (uint64_t)e.id))
         sel.push(gamma_make_key<false>((float)h, e.id));
     };
-
-    /* flush check: a pass pushes at most BS keys; where k2 + 2*BS fits
-     * the selector cap the check runs every second pass with margin 2*BS,
-     * otherwise every pass with margin BS (maybe_flush's invariant). The
-     * kill flag is loaded at the top of every pass and posted by thread 0
-     * on checking passes; kill[] slots alternate so one is next written
-     * two barriers later. */
+    /* flush check, kill poll and the two-set pass loop: the scheme of
+     * k_ivfpq_scan's fast path (reasons there) */
+    killed = sp.killed;
+    const unsigned niter = (sp.total + BS - 1) / BS;
     const bool flush_each = k2 + 2 * BS > GAMMA_SORT_CAP;
     const int fmargin = flush_each ? BS : 2 * BS;
-    const int *kf = kill_flag ? kill_flag : (const int *)probes;
-    auto pass = [&](GammaBinElem<U, NU> &nxt, const GammaBinElem<U, NU> &cur,
+    auto pass = [&](GammaBinElem<U, NU> &nxt, const GammaBinElem<U, NU> &cur_e,
                     unsigned it_nxt, int slot, bool check) {
       const int kv = __hip_atomic_load(kf, __ATOMIC_RELAXED,
                                        __HIP_MEMORY_SCOPE_AGENT);
       fetch(nxt, it_nxt);
-      consume(cur);
+      consume(cur_e);
       asm volatile("" ::"v"(kv));
       if (!check) return false;
       if (tid == 0) ch->kill[slot] = kill_flag ? kv : 0;
@@ -298,8 +246,6 @@ k_binivf_scan(int nq, int S, int W, int nprobe, int k2,
       retire(ea);
       retire(eb);
     }
-    /* barrier: the chunk is rewritten next round; doubles as the flush
-     * check an odd last pass skipped */
     sel.maybe_flush(fmargin);
   }
   sel.finish();

@@ -14,6 +14,7 @@
 
 #include "kernels.h"
 #include "select.hpp"
+#include "scan_walk.hpp"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -529,38 +530,16 @@ hipError_t gk::pq_lut_l2_dump(hipStream_t s, int nq, int d, int M, int ksub,
   return hipGetLastError();
 }
 
-/* Probe descriptors of the 8-bit fast path. A workgroup walks its probe
- * subsequence in chunks of at most GAMMA_SCAN_PCH lists; the lists of a
- * chunk form ONE flat index space [0, total): off[i] is the exclusive
- * prefix sum of the list sizes, so entry g belongs to the list i with
- * off[i] <= g < off[i+1]. Invalid probes and empty lists have size 0 and
- * drop out. The stream pointers carry the global address space, which
- * makes every list load a global_load (vmcnt only) — a generic pointer
- * would load with flat_load, which also ticks lgkmcnt and would make each
- * wait of the LDS gather drain the prefetch. */
-#define GAMMA_SCAN_PCH 32
-typedef const __attribute__((address_space(1))) uint32_t *gamma_gu32p;
-typedef const __attribute__((address_space(1))) uint8_t *gamma_gu8p;
-typedef const __attribute__((address_space(1))) float *gamma_gf32p;
-struct GammaScanChunk {
-  gamma_gu32p ids[GAMMA_SCAN_PCH];
-  gamma_gu8p codes[GAMMA_SCAN_PCH];
-  gamma_gf32p svals[GAMMA_SCAN_PCH];
-  float dis0[GAMMA_SCAN_PCH];
-  int sz[GAMMA_SCAN_PCH];
-  int off[GAMMA_SCAN_PCH + 1];
-  int ncons;    /* probes of the chunk whose flat space fits 31 bits */
-  int kill[2];  /* the kill flag as thread 0 last read it, per parity */
-  int state[2]; /* selector append counter */
-};
-
 /* dynamic LDS of k_ivfpq_scan: table, selector scratch + result, the
  * query (16-B aligned for the table builder's float4 reads), chunk */
-static size_t gamma_scan8_qs_off(int M, int k2) {
-  size_t o = (size_t)M * 256 * 4 + ((size_t)GAMMA_SORT_CAP + k2) * 8;
+__host__ __device__ static size_t gamma_scan8_sort_off(int M) {
+  return (size_t)M * 256 * 4;
+}
+__host__ __device__ static size_t gamma_scan8_qs_off(int M, int k2) {
+  size_t o = gamma_scan8_sort_off(M) + ((size_t)GAMMA_SORT_CAP + k2) * 8;
   return (o + 15) / 16 * 16;
 }
-static size_t gamma_scan8_chunk_off(int M, int k2, int d) {
+__host__ __device__ static size_t gamma_scan8_chunk_off(int M, int k2, int d) {
   return (gamma_scan8_qs_off(M, k2) + (size_t)d * 4 + 7) / 8 * 8;
 }
 static size_t gamma_scan8_smem(int M, int k2, int d) {
@@ -597,13 +576,11 @@ k_ivfpq_scan(int nq, int S, int d, int M, int nprobe, int k2,
   const int ksub = 256;
   const int dsub = d / M;
   float *lut = (float *)smem;                       /* M*ksub */
-  uint64_t *sortbuf = (uint64_t *)(smem + (size_t)M * ksub * 4);
+  uint64_t *sortbuf = (uint64_t *)(smem + gamma_scan8_sort_off(M));
   uint64_t *res = sortbuf + GAMMA_SORT_CAP;
-  const size_t qs_off =
-      ((size_t)M * ksub * 4 + ((size_t)GAMMA_SORT_CAP + k2) * 8 + 15) / 16 * 16;
-  float *qs = (float *)(smem + qs_off);             /* d */
+  float *qs = (float *)(smem + gamma_scan8_qs_off(M, k2)); /* d */
   GammaScanChunk *ch =
-      (GammaScanChunk *)(smem + (qs_off + (size_t)d * 4 + 7) / 8 * 8);
+      (GammaScanChunk *)(smem + gamma_scan8_chunk_off(M, k2, d));
 
   /* probe-split: S sub-workgroups per query, sub-block handles probes
    * p ≡ sub (mod S); partials merged by sort_rows afterwards. S>1 is
@@ -625,10 +602,7 @@ k_ivfpq_scan(int nq, int S, int d, int M, int nprobe, int k2,
     for (int e = threadIdx.x; e < M * ksub; e += blockDim.x) {
       int m = e >> 8, j = e & 255;
       const float *cw = codebooks + ((size_t)m * ksub + j) * dsub;
-      const float *qm = qs + m * dsub;
-      float acc = 0.0f;
-      for (int t = 0; t < dsub; t++) acc = fmaf(qm[t], cw[t], acc);
-      lut[e] = acc;
+      lut[e] = gamma_dot_serial(qs + m * dsub, cw, dsub);
     }
     __syncthreads();
   } else if (MW > 0) {
@@ -650,111 +624,64 @@ k_ivfpq_scan(int nq, int S, int d, int M, int nprobe, int k2,
   }
 
   if (MW > 0) {
-    /* Flattened, software-pipelined scan. Thread tid handles flat
-     * entries g = it*BS + tid of the current chunk, so the trip count is
-     * uniform across the block (the selector's barriers stay aligned)
-     * and only a chunk's last pass has idle lanes. The loads of pass
-     * it+1 (code words, id, S term) are issued into a second register
-     * set BEFORE the LDS gather of pass it: a workgroup's HBM latency
-     * runs under its own gather instead of in front of it. The loop is
-     * unrolled by two so the register sets alternate without copies and
-     * the wait in front of each gather is a counted vmcnt that leaves
-     * the prefetch outstanding. Push order differs from a list-by-list
-     * walk; the selector's top-k2 is exact under the (dist,id) total
-     * order, so results are unchanged. */
+    /* Flattened, software-pipelined scan over the chunked probe walk of
+     * scan_walk.hpp. Thread tid handles flat entries g = it*BS + tid of
+     * the current chunk, so the trip count is uniform across the block
+     * (the selector's barriers stay aligned) and only a chunk's last pass
+     * has idle lanes. The loads of pass it+1 (code words, id, S term) are
+     * issued into a second register set BEFORE the LDS gather of pass it:
+     * a workgroup's HBM latency runs under its own gather instead of in
+     * front of it. The loop is unrolled by two so the register sets
+     * alternate without copies and the wait in front of each gather is a
+     * counted vmcnt that leaves the prefetch outstanding. Push order
+     * differs from a list-by-list walk; the selector's top-k2 is exact
+     * under the (dist,id) total order, so results are unchanged. */
     const unsigned tid = threadIdx.x;
     const int np_sub = sub < nprobe ? (nprobe - sub + S - 1) / S : 0;
+    const int *kf = kill_flag ? kill_flag : (const int *)probes;
     bool killed = false;
     for (int c0 = 0; c0 < np_sub && !killed;) {
       const int cn = min(GAMMA_SCAN_PCH, np_sub - c0);
       if ((int)tid < cn) { /* one thread per probe of the chunk */
         const int p = sub + (c0 + (int)tid) * S;
-        int64_t ln = probes[(int64_t)q * nprobe + p];
-        GammaBucketDev bk;
-        bk.ids = nullptr; bk.data = nullptr; bk.svals = nullptr;
-        bk.size = 0;
+        const int64_t ln = probes[(int64_t)q * nprobe + p];
+        GammaBucketDev bk = gamma_null_bucket();
         float dis0 = 0.0f;
         if (ln >= 0 && ln < nlist) {
           bk = buckets[ln];
-          if (IP) { /* dis0 = dot(q, c), canonical serial order */
-            const float *cent = centroids + (size_t)ln * d;
-            for (int e = 0; e < d; e++) dis0 = fmaf(qs[e], cent[e], dis0);
-          } else {
+          if (IP) /* dis0 = dot(q, c), canonical serial order */
+            dis0 = gamma_dot_serial(qs, centroids + (size_t)ln * d, d);
+          else
             /* dis0 = the coarse probe distance (ivfpq.h:255
              * dis0=coarse_dis); the per-list table half arrives as the
              * per-vector S term */
             dis0 = probe_dists[(int64_t)q * nprobe + p];
-          }
         }
-        long long sz = bk.size < 0 ? 0 : bk.size;
-        if (sz > 0x7fffffffll) sz = 0x7fffffffll; /* ids are 31-bit */
-        ch->ids[tid] = (gamma_gu32p)bk.ids;
-        ch->codes[tid] = (gamma_gu8p)bk.data;
-        ch->svals[tid] = (gamma_gf32p)bk.svals;
-        ch->dis0[tid] = dis0;
-        ch->sz[tid] = (int)sz;
+        gamma_chunk_put(ch, tid, bk);
+        ch->per.dis0[tid] = dis0;
       }
-      if (tid == 0) {
-        /* in-flight kill (is_killed_every<1024> analog, ivfpq.h:927):
-         * agent-scope load (L2-served, so a host write during the kernel
-         * is visible — plain loads can stay L1-stale). ONE thread polls
-         * and the block reads its answer from LDS behind a barrier, so
-         * every thread takes the same exit. */
-        ch->kill[0] = kill_flag
-                          ? __hip_atomic_load(kill_flag, __ATOMIC_RELAXED,
-                                              __HIP_MEMORY_SCOPE_AGENT)
-                          : 0;
-        ch->ncons = cn;
-        ch->off[0] = 0;
-      }
-      __syncthreads();
-      if ((int)tid < cn) {
-        long long cum = 0;
-        for (int u = 0; u <= (int)tid; u++) cum += ch->sz[u];
-        if (cum > 0x7fffffffll) { /* flat space is 31-bit: end the chunk
-                                     before this probe (never the first) */
-          atomicMin(&ch->ncons, (int)tid);
-          cum = 0x7fffffffll;
-        }
-        ch->off[tid + 1] = (int)cum;
-      }
-      __syncthreads();
-      killed = ch->kill[0] != 0;
-      const int ncons = ch->ncons;
-      const unsigned total = killed ? 0u : (unsigned)ch->off[ncons];
-      const unsigned niter = (total + BS - 1) / BS;
-      c0 += ncons;
+      const GammaChunkSpan sp = gamma_chunk_close(ch, cn, kill_flag);
+      c0 += sp.ncons;
 
-      /* this thread's current list: entries [lstart, lend) */
-      int li = 0;
-      unsigned lstart = 0, lend = (unsigned)ch->off[1];
+      GammaListCursor cur;
+      cur.reset(ch, sp.total);
       gamma_gu32p pid = ch->ids[0];
       gamma_gu8p pcodes = ch->codes[0];
       gamma_gf32p psv = ch->svals[0];
-      float ldis0 = ch->dis0[0];
+      float ldis0 = ch->per.dis0[0];
 
-      /* Nothing is read past a list's size: a lane with no entry left
-       * (g >= total, only in a chunk's last pass) re-reads the chunk's
-       * last entry and is marked dead, instead of skipping its loads.
-       * The loads therefore sit in straight-line code; behind a branch
-       * the compiler's wait in front of the gather has to assume the
-       * prefetch may not have been issued and degrades to vmcnt(0). */
+      /* The loads sit in straight-line code (the cursor aliases a dead
+       * lane to the chunk's last entry instead of skipping its loads):
+       * behind a branch the compiler's wait in front of the gather has to
+       * assume the prefetch may not have been issued and degrades to
+       * vmcnt(0). */
       auto fetch = [&](GammaScanElem<MW> &e, unsigned it) {
-        const unsigned g0 = it * BS + tid;
-        e.live = g0 < total;
-        const unsigned g = e.live ? g0 : total - 1;
-        if (g >= lend) { /* LDS only */
-          do {
-            li++;
-            lend = (unsigned)ch->off[li + 1];
-          } while (g >= lend);
-          lstart = (unsigned)ch->off[li];
+        const unsigned j = cur.seek(ch, it * BS + tid, e.live, [&](int li) {
           pid = ch->ids[li];
           pcodes = ch->codes[li];
           psv = ch->svals[li];
-          ldis0 = ch->dis0[li];
-        }
-        const unsigned j = g - lstart;
+          ldis0 = ch->per.dis0[li];
+        });
         e.id = pid[j];
         if (!IP) e.sv = psv[j];
         e.dis0 = ldis0;
@@ -790,7 +717,6 @@ k_ivfpq_scan(int nq, int S, int d, int M, int nprobe, int k2,
           sel.push(gamma_make_key<IP>(dis, e.id));
         }
       };
-
       /* Flush check (one barrier). A pass pushes at most BS keys, so
        * where k2 + 2*BS fits the selector cap the check runs every
        * second pass with margin 2*BS — half the barriers, at the
@@ -807,7 +733,6 @@ k_ivfpq_scan(int nq, int S, int d, int M, int nprobe, int k2,
        * is next written two barriers later. */
       const bool flush_each = k2 + 2 * BS > GAMMA_SORT_CAP;
       const int fmargin = flush_each ? BS : 2 * BS;
-      const int *kf = kill_flag ? kill_flag : (const int *)probes;
       auto pass = [&](GammaScanElem<MW> &nxt, const GammaScanElem<MW> &cur,
                       unsigned it_nxt, int slot, bool check) {
         const int kv = __hip_atomic_load(kf, __ATOMIC_RELAXED,
@@ -820,6 +745,8 @@ k_ivfpq_scan(int nq, int S, int d, int M, int nprobe, int k2,
         sel.maybe_flush(fmargin);
         return ch->kill[slot] != 0;
       };
+      killed = sp.killed;
+      const unsigned niter = (sp.total + BS - 1) / BS;
       if (niter > 0) {
         GammaScanElem<MW> ea, eb;
         fetch(ea, 0);
@@ -852,13 +779,10 @@ k_ivfpq_scan(int nq, int S, int d, int M, int nprobe, int k2,
 
       float dis0;
       if (IP) {
-        if (threadIdx.x == 0) {  /* dis0 = dot(q, c), canonical order */
-          float acc = 0.0f;
-          for (int e = 0; e < d; e++) acc = fmaf(qs[e], cent[e], acc);
-          ch->dis0[0] = acc;
-        }
+        if (threadIdx.x == 0) /* dis0 = dot(q, c), canonical order */
+          ch->per.dis0[0] = gamma_dot_serial(qs, cent, d);
         __syncthreads();
-        dis0 = ch->dis0[0];
+        dis0 = ch->per.dis0[0];
       } else {
         dis0 = probe_dists[(int64_t)q * nprobe + p];
       }
@@ -922,12 +846,15 @@ k_ivfpq_scan(int nq, int S, int d, int M, int nprobe, int k2,
 #define GAMMA_WIDE_MS 32 /* sub-quantizers per table slice: 32 KB of LDS */
 #define GAMMA_WIDE_E 4   /* entries per thread per tile */
 
-static size_t gamma_wide_qs_off(int k2) {
-  size_t o = (size_t)GAMMA_WIDE_MS * 256 * 4 +
-             ((size_t)GAMMA_SORT_CAP + k2) * 8;
+__host__ __device__ static size_t gamma_wide_sort_off() {
+  return (size_t)GAMMA_WIDE_MS * 256 * 4;
+}
+__host__ __device__ static size_t gamma_wide_qs_off(int k2) {
+  size_t o = gamma_wide_sort_off() + ((size_t)GAMMA_SORT_CAP + k2) * 8;
   return (o + 15) / 16 * 16;
 }
-static size_t gamma_wide_chunk_off(int k2, int d, bool ip) {
+__host__ __device__ static size_t gamma_wide_chunk_off(int k2, int d,
+                                                       bool ip) {
   return (gamma_wide_qs_off(k2) + (ip ? (size_t)d * 4 : 0) + 7) / 8 * 8;
 }
 static size_t gamma_wide_smem(int k2, int d, bool ip) {
@@ -989,14 +916,11 @@ k_ivfpq_scan_wide(int nq, int S, int d, int M, int nprobe, int k2,
   constexpr unsigned T = (unsigned)BS * E;
   constexpr int NT = MS * 256 / 4 / BS; /* table float4s per thread */
   float *lut = (float *)smem;                       /* MS*256 */
-  uint64_t *sortbuf = (uint64_t *)(smem + (size_t)MS * 256 * 4);
+  uint64_t *sortbuf = (uint64_t *)(smem + gamma_wide_sort_off());
   uint64_t *res = sortbuf + GAMMA_SORT_CAP;
-  const size_t qs_off =
-      ((size_t)MS * 256 * 4 + ((size_t)GAMMA_SORT_CAP + k2) * 8 + 15) / 16 *
-      16;
-  float *qs = (float *)(smem + qs_off);             /* d, IP only */
-  GammaScanChunk *ch = (GammaScanChunk *)(
-      smem + (qs_off + (IP ? (size_t)d * 4 : 0) + 7) / 8 * 8);
+  float *qs = (float *)(smem + gamma_wide_qs_off(k2)); /* d, IP only */
+  GammaScanChunk *ch =
+      (GammaScanChunk *)(smem + gamma_wide_chunk_off(k2, d, IP));
 
   const int bq = blockIdx.x / S;
   const int sub = blockIdx.x - bq * S;
@@ -1020,90 +944,53 @@ k_ivfpq_scan_wide(int nq, int S, int d, int M, int nprobe, int k2,
     int misaligned = 0;
     if ((int)tid < cn) { /* one thread per probe of the chunk */
       const int p = sub + (c0 + (int)tid) * S;
-      int64_t ln = probes[(int64_t)q * nprobe + p];
-      GammaBucketDev bk;
-      bk.ids = nullptr; bk.data = nullptr; bk.svals = nullptr;
-      bk.size = 0;
+      const int64_t ln = probes[(int64_t)q * nprobe + p];
+      GammaBucketDev bk = gamma_null_bucket();
       float dis0 = 0.0f;
       if (ln >= 0 && ln < nlist) {
         bk = buckets[ln];
-        if (IP) { /* dis0 = dot(q, c), canonical serial order */
-          const float *cent = centroids + (size_t)ln * d;
-          for (int e = 0; e < d; e++) dis0 = fmaf(qs[e], cent[e], dis0);
-        } else {
+        if (IP) /* dis0 = dot(q, c), canonical serial order */
+          dis0 = gamma_dot_serial(qs, centroids + (size_t)ln * d, d);
+        else
           dis0 = probe_dists[(int64_t)q * nprobe + p];
-        }
       }
-      long long sz = bk.size < 0 ? 0 : bk.size;
-      if (sz > 0x7fffffffll) sz = 0x7fffffffll; /* ids are 31-bit */
-      ch->ids[tid] = (gamma_gu32p)bk.ids;
-      ch->codes[tid] = (gamma_gu8p)bk.data;
-      ch->svals[tid] = (gamma_gf32p)bk.svals;
-      ch->dis0[tid] = dis0;
-      ch->sz[tid] = (int)sz;
+      const int sz = gamma_chunk_put(ch, tid, bk);
+      ch->per.dis0[tid] = dis0;
       misaligned = sz > 0 && ((uintptr_t)bk.data & 15) != 0;
     }
-    if (tid == 0) {
-      ch->kill[0] = kill_flag
-                        ? __hip_atomic_load(kill_flag, __ATOMIC_RELAXED,
-                                            __HIP_MEMORY_SCOPE_AGENT)
-                        : 0;
-      ch->ncons = cn;
-      ch->off[0] = 0;
-    }
-    /* barrier + vote: 16-byte code loads need every list of the chunk
-     * 16-byte aligned (and M % 16 == 0) */
-    const bool a16 = !__syncthreads_or(misaligned) && (M & 15) == 0;
-    if ((int)tid < cn) {
-      long long cum = 0;
-      for (int u = 0; u <= (int)tid; u++) cum += ch->sz[u];
-      if (cum > 0x7fffffffll) { /* flat space is 31-bit: end the chunk
-                                   before this probe (never the first) */
-        atomicMin(&ch->ncons, (int)tid);
-        cum = 0x7fffffffll;
-      }
-      ch->off[tid + 1] = (int)cum;
-    }
-    __syncthreads();
-    killed = ch->kill[0] != 0;
-    const int ncons = ch->ncons;
-    const unsigned total = killed ? 0u : (unsigned)ch->off[ncons];
+    /* the close's first barrier carries the vote: 16-byte code loads need
+     * every list of the chunk 16-byte aligned (and M % 16 == 0) */
+    const GammaChunkSpan sp =
+        gamma_chunk_close<true>(ch, cn, kill_flag, &misaligned);
+    const bool a16 = !misaligned && (M & 15) == 0;
+    killed = sp.killed;
+    const unsigned total = sp.total;
     const unsigned ntile = (total + T - 1) / T;
-    c0 += ncons;
+    c0 += sp.ncons;
 
-    /* this thread's current list: entries [lstart, lend). Its flat
-     * indices ascend over (tile, e), so the walk only moves forward. */
-    int li = 0;
-    unsigned lstart = 0, lend = (unsigned)ch->off[1];
+    GammaListCursor cur;
+    cur.reset(ch, total);
     gamma_gu32p pid = ch->ids[0];
     gamma_gu8p pcodes = ch->codes[0];
     gamma_gf32p psv = ch->svals[0];
-    float ldis0 = ch->dis0[0];
+    float ldis0 = ch->per.dis0[0];
 
     for (unsigned tile = 0; tile < ntile; tile++) {
-      /* Nothing is read past a list's size: a slot with no entry (only
-       * in a chunk's last tile) aliases the chunk's last entry and
-       * carries the skip bit. */
+      /* a slot with no entry (only in a chunk's last tile) carries the
+       * skip bit */
       gamma_gu32p cw[E];
       uint32_t id[E];
       float dis[E];
 #pragma unroll
       for (int e = 0; e < E; e++) {
-        const unsigned g0 = tile * T + (unsigned)e * BS + tid;
-        const bool live = g0 < total;
-        const unsigned g = live ? g0 : total - 1;
-        if (g >= lend) { /* LDS only */
-          do {
-            li++;
-            lend = (unsigned)ch->off[li + 1];
-          } while (g >= lend);
-          lstart = (unsigned)ch->off[li];
-          pid = ch->ids[li];
-          pcodes = ch->codes[li];
-          psv = ch->svals[li];
-          ldis0 = ch->dis0[li];
-        }
-        const unsigned j = g - lstart;
+        bool live;
+        const unsigned j = cur.seek(
+            ch, tile * T + (unsigned)e * BS + tid, live, [&](int li) {
+              pid = ch->ids[li];
+              pcodes = ch->codes[li];
+              psv = ch->svals[li];
+              ldis0 = ch->per.dis0[li];
+            });
         uint32_t idv = pid[j];
         if (!live ||
             (!(idv >> 31) && gamma_bitmap_test(bitmap, (uint64_t)idv)))
@@ -1204,9 +1091,7 @@ __global__ void k_pq_iptable(int64_t total, int d, int M,
   const int mj = (int)(e - q * M * 256); /* m*256 + j */
   const float *cw = codebooks + (size_t)mj * dsub;
   const float *qm = queries + q * d + (mj >> 8) * dsub;
-  float acc = 0.0f;
-  for (int t = 0; t < dsub; t++) acc = fmaf(qm[t], cw[t], acc);
-  out[e] = acc;
+  out[e] = gamma_dot_serial(qm, cw, dsub);
 }
 
 hipError_t gk::pq_tables_ip(hipStream_t s, int nq, int d, int M,

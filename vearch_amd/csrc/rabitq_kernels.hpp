@@ -2,8 +2,7 @@
  * rabitq_kernels.hpp — kernels of the IVFRABITQ index (1-bit RaBitQ codes,
  * gamma_index_ivfrabitq.cc with nb_bits = 1). Included at the end of
  * kernels.hip after binary_kernels.hpp: it uses that file's gamma_bin_load,
- * and kernels.hip's WG, GAMMA_SCAN_PCH, the global-address-space pointer
- * typedefs and the GAMMA_SCAN_BS launch knob.
+ * kernels.hip's WG and GAMMA_SCAN_BS launch knob, and scan_walk.hpp.
  *
  * An entry of a d-dimensional table is EW = d/32 + 2 little-endian words:
  * W = d/32 sign words (bit j of the vector is bit j&31 of word j>>5, the
@@ -144,12 +143,9 @@ hipError_t gk::rabitq_sval_buckets(hipStream_t s, int nlist, int d,
 }
 
 /* ---------------------------------------------------- RaBitQ IVF fused scan
- * The contract and the flat, chunked, prefetching walk of k_binivf_scan and
- * of k_ivfpq_scan's fast path (see there): a workgroup serves (query,
- * probe-split sub-block), takes its probes in chunks of <= GAMMA_SCAN_PCH
- * lists whose entries form one flat index space, thread tid handles flat
- * entry it*BS + tid, and the loads of pass it+1 are issued before pass it
- * is consumed.
+ * The contract of k_binivf_scan and of k_ivfpq_scan's fast path, and their
+ * chunked probe walk (scan_walk.hpp): a workgroup serves (query,
+ * probe-split sub-block).
  *
  * Query table: lut[i][n], i < d/4, n < 16 = sum of q[4i + b] over the bits
  * b set in n, ascending b. A row is 16 consecutive LDS banks, so the 64
@@ -168,17 +164,11 @@ hipError_t gk::rabitq_sval_buckets(hipStream_t s, int nlist, int d,
  * NU units held in registers and double-buffered. NU == 0: the entry is
  * streamed in units of U (2 when d/32 is even, else 1) at consume time and
  * only id and sval are prefetched. */
-struct GammaRbqChunk {
-  gamma_gu32p ids[GAMMA_SCAN_PCH];
-  gamma_gu8p codes[GAMMA_SCAN_PCH];
-  gamma_gf32p svals[GAMMA_SCAN_PCH];
+struct GammaRbqPer {
   float qc2[GAMMA_SCAN_PCH];
   float sqc[GAMMA_SCAN_PCH];
-  int sz[GAMMA_SCAN_PCH];
-  int off[GAMMA_SCAN_PCH + 1];
-  int ncons;
-  int kill[2];
-  int state[2];
+};
+struct GammaRbqChunk : GammaChunkT<GammaRbqPer> {
   float qq; /* ||q||^2 */
 };
 
@@ -191,10 +181,15 @@ struct GammaRbqElem {
   bool live;
 };
 
-static size_t gamma_rbq_qs_off(int d, int k2) {
-  return (size_t)d * 16 + ((size_t)GAMMA_SORT_CAP + k2) * 8;
+/* dynamic LDS of k_rabitq_scan: table, selector scratch + result, query,
+ * chunk */
+__host__ __device__ static size_t gamma_rbq_sort_off(int d) {
+  return (size_t)d * 16;
 }
-static size_t gamma_rbq_chunk_off(int d, int k2) {
+__host__ __device__ static size_t gamma_rbq_qs_off(int d, int k2) {
+  return gamma_rbq_sort_off(d) + ((size_t)GAMMA_SORT_CAP + k2) * 8;
+}
+__host__ __device__ static size_t gamma_rbq_chunk_off(int d, int k2) {
   return (gamma_rbq_qs_off(d, k2) + (size_t)d * 4 + 7) / 8 * 8;
 }
 static size_t gamma_rbq_smem(int d, int k2) {
@@ -248,12 +243,10 @@ k_rabitq_scan(int nq, int S, int d, int nprobe, int k2,
               const int *__restrict__ kill_flag) {
   extern __shared__ char smem[];
   float *lut = (float *)smem; /* d/4 x 16 */
-  uint64_t *sortbuf = (uint64_t *)(smem + (size_t)d * 16);
+  uint64_t *sortbuf = (uint64_t *)(smem + gamma_rbq_sort_off(d));
   uint64_t *res = sortbuf + GAMMA_SORT_CAP;
-  float *qs = (float *)(res + k2); /* d */
-  GammaRbqChunk *ch = (GammaRbqChunk *)(
-      smem + (((size_t)d * 16 + ((size_t)GAMMA_SORT_CAP + k2) * 8 +
-               (size_t)d * 4 + 7) / 8 * 8));
+  float *qs = (float *)(smem + gamma_rbq_qs_off(d, k2)); /* d */
+  GammaRbqChunk *ch = (GammaRbqChunk *)(smem + gamma_rbq_chunk_off(d, k2));
 
   const int q = blockIdx.x / S;
   const int sub = blockIdx.x - q * S;
@@ -288,6 +281,7 @@ k_rabitq_scan(int nq, int S, int d, int nprobe, int k2,
   const int EW = W + 2;
 
   const int np_sub = sub < nprobe ? (nprobe - sub + S - 1) / S : 0;
+  const int *kf = kill_flag ? kill_flag : (const int *)probes;
   bool killed = false;
   for (int c0 = 0; c0 < np_sub && !killed;) {
     const int cn = min(GAMMA_SCAN_PCH, np_sub - c0);
@@ -301,75 +295,31 @@ k_rabitq_scan(int nq, int S, int d, int nprobe, int k2,
       gamma_rbq_qc(qs, ok ? centroids + (size_t)ln * d : nullptr, d,
                    ok ? l : -1, s2, s1);
       if (pi < cn && l == 0) {
-        GammaBucketDev bk;
-        bk.ids = nullptr; bk.data = nullptr; bk.svals = nullptr;
-        bk.size = 0;
+        GammaBucketDev bk = gamma_null_bucket();
         if (ok) bk = buckets[ln];
-        long long sz = bk.size < 0 ? 0 : bk.size;
-        if (sz > 0x7fffffffll) sz = 0x7fffffffll; /* ids are 31-bit */
-        ch->ids[pi] = (gamma_gu32p)bk.ids;
-        ch->codes[pi] = (gamma_gu8p)bk.data;
-        ch->svals[pi] = (gamma_gf32p)bk.svals;
-        ch->qc2[pi] = s2;
-        ch->sqc[pi] = s1;
-        ch->sz[pi] = (int)sz;
+        gamma_chunk_put(ch, pi, bk);
+        ch->per.qc2[pi] = s2;
+        ch->per.sqc[pi] = s1;
       }
     }
-    if (tid == 0) {
-      /* in-flight kill: agent-scope load, one thread polls and the block
-       * reads its answer from LDS behind the barrier */
-      ch->kill[0] = kill_flag
-                        ? __hip_atomic_load(kill_flag, __ATOMIC_RELAXED,
-                                            __HIP_MEMORY_SCOPE_AGENT)
-                        : 0;
-      ch->ncons = cn;
-      ch->off[0] = 0;
-    }
-    __syncthreads();
-    if ((int)tid < cn) {
-      long long cum = 0;
-      for (int u = 0; u <= (int)tid; u++) cum += ch->sz[u];
-      if (cum > 0x7fffffffll) { /* flat space is 31-bit: end the chunk
-                                   before this probe (never the first) */
-        atomicMin(&ch->ncons, (int)tid);
-        cum = 0x7fffffffll;
-      }
-      ch->off[tid + 1] = (int)cum;
-    }
-    __syncthreads();
-    killed = ch->kill[0] != 0;
-    const int ncons = ch->ncons;
-    const unsigned total = killed ? 0u : (unsigned)ch->off[ncons];
-    const unsigned niter = (total + BS - 1) / BS;
-    c0 += ncons;
+    const GammaChunkSpan sp = gamma_chunk_close(ch, cn, kill_flag);
+    c0 += sp.ncons;
 
-    /* this thread's current list: entries [lstart, lend) */
-    int li = 0;
-    unsigned lstart = 0, lend = (unsigned)ch->off[1];
+    GammaListCursor cur;
+    cur.reset(ch, sp.total);
     gamma_gu32p pid = ch->ids[0];
     gamma_gu32p pcodes = (gamma_gu32p)ch->codes[0];
     gamma_gf32p psv = ch->svals[0];
-    float lqc2 = ch->qc2[0], lsqc = ch->sqc[0];
+    float lqc2 = ch->per.qc2[0], lsqc = ch->per.sqc[0];
 
-    /* a lane with no entry left re-reads the chunk's last entry and is
-     * marked dead, so the loads sit in straight-line code */
     auto fetch = [&](GammaRbqElem<U, NU> &e, unsigned it) {
-      const unsigned g0 = it * BS + tid;
-      e.live = g0 < total;
-      const unsigned g = e.live ? g0 : total - 1;
-      if (g >= lend) { /* LDS only */
-        do {
-          li++;
-          lend = (unsigned)ch->off[li + 1];
-        } while (g >= lend);
-        lstart = (unsigned)ch->off[li];
+      const unsigned j = cur.seek(ch, it * BS + tid, e.live, [&](int li) {
         pid = ch->ids[li];
         pcodes = (gamma_gu32p)ch->codes[li];
         psv = ch->svals[li];
-        lqc2 = ch->qc2[li];
-        lsqc = ch->sqc[li];
-      }
-      const unsigned j = g - lstart;
+        lqc2 = ch->per.qc2[li];
+        lsqc = ch->per.sqc[li];
+      });
       e.id = pid[j];
       e.sv = psv[j];
       e.qc2 = lqc2;
@@ -385,8 +335,6 @@ k_rabitq_scan(int nq, int S, int d, int nprobe, int k2,
         }
       }
     };
-    /* name an entry's registers so its loads are retired by one counted
-     * wait and none stays pending into the next prefetch */
     auto retire = [&](const GammaRbqElem<U, NU> &e) {
       if constexpr (NU > 0) {
 #pragma unroll
@@ -431,16 +379,18 @@ k_rabitq_scan(int nq, int S, int d, int nprobe, int k2,
       }
     };
 
-    /* flush check and kill poll: the scheme of k_binivf_scan */
+    /* flush check, kill poll and the two-set pass loop: the scheme of
+     * k_ivfpq_scan's fast path (reasons there) */
+    killed = sp.killed;
+    const unsigned niter = (sp.total + BS - 1) / BS;
     const bool flush_each = k2 + 2 * BS > GAMMA_SORT_CAP;
     const int fmargin = flush_each ? BS : 2 * BS;
-    const int *kf = kill_flag ? kill_flag : (const int *)probes;
-    auto pass = [&](GammaRbqElem<U, NU> &nxt, const GammaRbqElem<U, NU> &cur,
+    auto pass = [&](GammaRbqElem<U, NU> &nxt, const GammaRbqElem<U, NU> &cur_e,
                     unsigned it_nxt, int slot, bool check) {
       const int kv = __hip_atomic_load(kf, __ATOMIC_RELAXED,
                                        __HIP_MEMORY_SCOPE_AGENT);
       fetch(nxt, it_nxt);
-      consume(cur);
+      consume(cur_e);
       asm volatile("" ::"v"(kv));
       if (!check) return false;
       if (tid == 0) ch->kill[slot] = kill_flag ? kv : 0;
@@ -460,8 +410,6 @@ k_rabitq_scan(int nq, int S, int d, int nprobe, int k2,
       retire(ea);
       retire(eb);
     }
-    /* barrier: the chunk is rewritten next round; doubles as the flush
-     * check an odd last pass skipped */
     sel.maybe_flush(fmargin);
   }
   sel.finish();

@@ -491,12 +491,22 @@ def hamming_matrix(Q, B):
     return out.cpu().numpy()
 
 
+def _kill_dev(kill_flag):
+    """the kill_flag argument of binivf_scan / rabitq_scan: False or None
+    passes NULL, True a device int left at 0, an int (0 or 1) a device int
+    holding that value (1 = a flag raised before the launch)."""
+    if kill_flag is None or kill_flag is False:
+        return None
+    return torch.full((1,), 0 if kill_flag is True else int(kill_flag),
+                      dtype=torch.int32, device="cuda")
+
+
 def binivf_scan(lists, probes, queries, S, k2, bitmap=None, kill_flag=False):
     """One gk::binivf_scan launch on host arrays. lists: one (ids uint32
     (n,), codes uint8 (n, d/8)) per inverted list (n = 0 is legal), each
     array in its own device allocation; probes int64 (nq, nprobe) may hold
     -1 and ids >= nlist; queries uint8 (nq, d/8); bitmap: optional uint32
-    words; kill_flag: pass a device int left at 0 instead of NULL.
+    words; kill_flag: see _kill_dev.
     Returns (keys uint64 (nq, S, k2), dists, ids): the raw partial rows
     and their gk::sort_rows merge to the top-k2 (-1 / -1 padded; None,
     None where S * k2 exceeds what sort_rows takes)."""
@@ -517,8 +527,7 @@ def binivf_scan(lists, probes, queries, S, k2, bitmap=None, kill_flag=False):
         rows.append([x.data_ptr() if n else 0 for x in t] + [0, n])
     bk_d = torch.tensor(rows, dtype=torch.int64).reshape(-1, 4).cuda()
     bm_d = None if bitmap is None else bitmap_to_dev(bitmap)
-    kf_d = torch.zeros(1, dtype=torch.int32, device="cuda") \
-        if kill_flag else None
+    kf_d = _kill_dev(kill_flag)
     keys = torch.full((nq, S, k2), 0x5A5A5A5A5A5A5A5A, dtype=torch.int64,
                       device="cuda")
     _call("GammaKTestBinivfScan", nq, S, W, nprobe, k2,
@@ -580,7 +589,7 @@ def rabitq_scan(lists, probes, queries, centroids, S, k2, ip, bitmap=None,
     (n = 0 is legal), each array in its own device allocation; probes int64
     (nq, nprobe) may hold -1 and ids >= nlist; queries float32 (nq, d);
     centroids float32 (nlist, d); bitmap: optional uint32 words; kill_flag:
-    pass a device int left at 0 instead of NULL.
+    see _kill_dev.
     Returns (keys uint64 (nq, S, k2), scores, ids): the raw partial rows
     and their gk::sort_rows merge to the top-k2 (-1 / -1 padded)."""
     f32 = lambda a: torch.from_numpy(  # noqa: E731
@@ -608,8 +617,7 @@ def rabitq_scan(lists, probes, queries, centroids, S, k2, ip, bitmap=None,
         rows.append([x.data_ptr() if n else 0 for x in t] + [n])
     bk_d = torch.tensor(rows, dtype=torch.int64).reshape(-1, 4).cuda()
     bm_d = None if bitmap is None else bitmap_to_dev(bitmap)
-    kf_d = torch.zeros(1, dtype=torch.int32, device="cuda") \
-        if kill_flag else None
+    kf_d = _kill_dev(kill_flag)
     keys = torch.full((nq, S, k2), 0x5A5A5A5A5A5A5A5A, dtype=torch.int64,
                       device="cuda")
     _call("GammaKTestRabitqScan", nq, S, d, nprobe, k2, _p(q_d), _p(c_d),
