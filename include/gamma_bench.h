@@ -192,6 +192,37 @@ int GammaKTestIvfpqScan(int nq, int S, int d, int M, int ksub, int nprobe,
 int GammaKTestPqTablesIp(int nq, int d, int M, const float *queries,
                          const float *codebooks, float *out);
 int GammaKTestIvfpqWideInfo(int d, int M, int ksub, int k2, int *out5);
+/* gk::ivfflat_scan: buckets_dev as for GammaKTestIvfpqScan with `data` =
+ * d fp32 per entry and svals 0; out_keys nq x k2; bitmap may be 0. */
+int GammaKTestIvfflatScan(int nq, int d, int nprobe, int k2,
+                          const float *queries, const void *buckets_dev,
+                          int nlist, const int64_t *probes,
+                          const uint32_t *bitmap, int ip, uint64_t *out_keys);
+/* Ingest and table kernels. PqTablesB: btab nlist x M x ksub. PqSterm:
+ * codes are bucket-format entries (M bytes, or M/2 packed bytes at ksub =
+ * 16), asg may be 0 (every vector in list asg_const). PqStermBuckets /
+ * RabitqSvalBuckets: bks_dev is nlist GammaBucketDev whose svals are
+ * written (a bucket with svals 0 or size 0 is skipped). BucketScatter:
+ * segs_dev is nseg GammaScatterSeg (csrc/kernels.h), i.e. 5 x 8-byte fields
+ * per segment: ids_dst, data_dst, sval_dst (or 0), src_start, count;
+ * svals_src may be 0. */
+int GammaKTestPqTablesB(int d, int M, int ksub, int nlist,
+                        const float *centroids, const float *codebooks,
+                        float *btab);
+int GammaKTestPqSterm(int64_t n, int M, int ksub, int nlist,
+                      const uint8_t *codes, const int32_t *asg, int asg_const,
+                      const float *btab, float *out);
+int GammaKTestPqStermBuckets(int nlist, int M, int ksub, const void *bks_dev,
+                             const float *btab);
+int GammaKTestBucketScatter(int nseg, const void *segs_dev,
+                            const uint32_t *ids_src, const uint8_t *data_src,
+                            const float *svals_src, int entry_bytes);
+int GammaKTestResiduals(int64_t n, int d, const float *x,
+                        const float *centroids, const int32_t *assign,
+                        float *out);
+int GammaKTestRowNorms(const float *v, int64_t n, int d, float *norms);
+int GammaKTestExtractProbe0(int nq, int nprobe, const int64_t *probes,
+                            int32_t *out);
 
 /* BINARYIVF kernels (W = d/32 u32 words per vector, LSB-first bits):
  * HammingMatrix out[i*n+j] = popcount(Q_i xor B_j) as f32; BinivfScan has
@@ -227,6 +258,8 @@ int GammaKTestRabitqScan(int nq, int S, int d, int nprobe, int k2,
                          const void *buckets_dev, int nlist,
                          const int64_t *probes, const uint32_t *bitmap,
                          int ip, uint64_t *out_keys, const int *kill_flag);
+int GammaKTestRabitqSvalBuckets(int nlist, int d, const void *bks_dev,
+                                const float *centroids);
 
 #ifdef __cplusplus
 }

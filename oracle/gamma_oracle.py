@@ -65,6 +65,12 @@ class RefLib:
                 f32p]
             lib.oracle_adc_table_ip.argtypes = [
                 ctypes.c_int, ctypes.c_int, ctypes.c_int, f32p, f32p, f32p]
+            lib.oracle_pct1_a_table.argtypes = [
+                ctypes.c_int, ctypes.c_int, ctypes.c_int, f32p, f32p, f32p]
+            lib.oracle_pct1_b_table.argtypes = [
+                ctypes.c_int, ctypes.c_int, ctypes.c_int, f32p, f32p, f32p]
+            lib.oracle_ip.restype = ctypes.c_float
+            lib.oracle_ip.argtypes = [f32p, f32p, ctypes.c_int]
             lib.oracle_ivfpq_search_pct1.argtypes = [
                 ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                 ctypes.c_int, f32p, f32p, f32p, i64p, i64p, u8p,
@@ -92,6 +98,49 @@ def _up8(a):
 
 def _c(a, dtype):
     return np.ascontiguousarray(a, dtype=dtype)
+
+
+# ------------------------------------------ serial-fmaf chains, as arrays
+def _table_rows(fn, rows, codebooks, M, ksub):
+    rows = _c(rows, np.float32)
+    cb = _c(codebooks, np.float32)
+    n, d = rows.shape
+    assert d % M == 0 and cb.size == ksub * d
+    out = np.full((n, M, ksub), np.nan, dtype=np.float32)
+    for i in range(n):
+        fn(d, M, ksub, _fp(rows[i]), _fp(cb), _fp(out[i]))
+    return out
+
+
+def pct1_a_table(queries, codebooks, M, ksub):
+    """oracle_pct1_a_table per query: (nq, M, ksub) f32,
+    A[q][m][j] = fmaf(-2, q_m . cw_mj, ||cw_mj||^2)."""
+    return _table_rows(RefLib.lib().oracle_pct1_a_table, queries, codebooks,
+                       M, ksub)
+
+
+def pct1_b_table(centroids, codebooks, M, ksub):
+    """oracle_pct1_b_table per list: (nlist, M, ksub) f32,
+    B[l][m][j] = 2 * (c_l,m . cw_mj)."""
+    return _table_rows(RefLib.lib().oracle_pct1_b_table, centroids,
+                       codebooks, M, ksub)
+
+
+def adc_table_ip(queries, codebooks, M, ksub):
+    """oracle_adc_table_ip per query: (nq, M, ksub) f32, T = q_m . cw_mj."""
+    return _table_rows(RefLib.lib().oracle_adc_table_ip, queries, codebooks,
+                       M, ksub)
+
+
+def ip_serial(x, y):
+    """oracle_ip of every row pair: x (n, d), y (m, d) -> (n, m) f32, each
+    entry one sequential fmaf chain over d."""
+    x, y = _c(x, np.float32), _c(y, np.float32)
+    assert x.ndim == 2 and y.ndim == 2 and x.shape[1] == y.shape[1]
+    fn = RefLib.lib().oracle_ip
+    d = x.shape[1]
+    return np.array([[fn(_fp(a), _fp(b), d) for b in y] for a in x],
+                    dtype=np.float32).reshape(x.shape[0], y.shape[0])
 
 
 # ------------------------------------------------------------ data synthesis

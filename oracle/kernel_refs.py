@@ -165,3 +165,40 @@ def pack4(codes):
     2b in bits 0-3 and code 2b+1 in bits 4-7."""
     codes = np.asarray(codes, dtype=np.uint8)
     return (codes[:, 0::2] | (codes[:, 1::2] << 4)).astype(np.uint8)
+
+
+def unpack4(packed):
+    """inverse of pack4: (n, M/2) bytes -> (n, M) codes below 16."""
+    packed = np.asarray(packed, dtype=np.uint8)
+    out = np.empty((packed.shape[0], 2 * packed.shape[1]), dtype=np.uint8)
+    out[:, 0::2] = packed & 15
+    out[:, 1::2] = packed >> 4
+    return out
+
+
+# ------------------------------------------------------------- ADC chains
+def adc_chain(start, table, codes):
+    """start[i] + table[0][codes[i][0]] + table[1][codes[i][1]] + ...: one
+    fp32 add per sub-quantizer in ascending m, rounded after every add.
+    start: f32 scalar or (n,); table (M, ksub) f32; codes (n, M)."""
+    table = np.asarray(table, dtype=np.float32)
+    codes = np.asarray(codes)
+    acc = np.broadcast_to(np.asarray(start, dtype=np.float32),
+                          codes.shape[:1]).copy()
+    for m in range(table.shape[0]):
+        acc = (acc + table[m, codes[:, m]]).astype(np.float32)
+    return acc
+
+
+def sterm_ref(btab, codes, asg):
+    """gk::pq_sterm: out[i] = adc_chain(0, btab[asg[i]], codes[i]); 0.0
+    where asg[i] is outside [0, nlist). btab (nlist, M, ksub), codes (n, M)
+    one code per byte, asg (n,) ints."""
+    btab = np.asarray(btab, dtype=np.float32)
+    codes = np.asarray(codes)
+    asg = np.asarray(asg)
+    out = np.zeros(codes.shape[0], dtype=np.float32)
+    for ln in range(btab.shape[0]):
+        sel = asg == ln
+        out[sel] = adc_chain(np.float32(0.0), btab[ln], codes[sel])
+    return out

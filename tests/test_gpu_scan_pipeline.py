@@ -31,23 +31,28 @@ NDOC = 8192  # ids are < NDOC (the bitmap's extent)
 DMS = [(32, 16), (64, 16), (128, 32)]  # dsub 2 (scalar chain), 4, 4
 
 
-def _probe_tables():
-    """name -> int64 (nq, nprobe) probe table."""
+def _probe_tables(SIZES=SIZES, small=(63, 64, 65)):
+    """name -> int64 (nq, nprobe) probe table. SIZES: the list sizes
+    (NLIST of them; 255..257, 511..513, 1100, 1, three empty lists and the
+    three `small` sizes must occur)."""
+    assert len(SIZES) == NLIST
+    L = {s: SIZES.index(s) for s in set(SIZES)}
+    s0, s1, s2 = small
     E = [i for i, s in enumerate(SIZES) if s == 0]  # the empty lists
     tiny = [i for i, s in enumerate(SIZES) if s <= 1]  # sizes 0 and 1
     rng = np.random.default_rng(5)
     a = np.array([
         [E[0], E[1], E[2], E[0], E[1], E[2], E[0], E[1]],  # all empty
-        [-1, L[1100], NLIST, L[513], -1, NLIST + 7, L[257], L[65]],
+        [-1, L[1100], NLIST, L[513], -1, NLIST + 7, L[257], L[s2]],
         [E[0], L[511], E[1], -1, E[2], NLIST, E[0], E[1]],  # total 511
         [L[512], E[0], E[1], -1, E[2], NLIST, E[0], E[1]],  # total 512
         [E[0], E[1], -1, E[2], NLIST, E[0], E[1], L[513]],  # total 513
         [L[255], E[0], E[1], -1, E[2], NLIST, E[0], E[1]],  # total 255
         [E[0], L[256], E[1], -1, E[2], NLIST, E[0], E[1]],  # total 256
-        [L[63], L[64], L[65], L[1], L[64], E[0], -1, E[1]],  # total 257
+        [L[s0], L[s1], L[s2], L[1], L[s1], E[0], -1, E[1]],  # total 257
     ], dtype=np.int64)
     assert [sum(SIZES[x] for x in r if 0 <= x < NLIST) for r in a[2:]] == [
-        511, 512, 513, 255, 256, 257]
+        511, 512, 513, 255, 256, s0 + 2 * s1 + s2 + 1]
     one = np.array([[L[1100]], [E[0]], [-1], [L[1]], [NLIST]],
                    dtype=np.int64)  # nprobe = 1; three rows with total 0
     # more probes than a chunk holds, over tiny lists (ids repeat)

@@ -16,6 +16,11 @@ KTEST_EXPORTS = [
     "GammaKTestSelectRowsFull", "GammaKTestArgminRows", "GammaKTestRerank",
     "GammaKTestSortRows", "GammaKTestUnpackKeys", "GammaKTestPqEncode",
     "GammaKTestPqEncodePack4", "GammaKTestFlatStreamScan",
+    "GammaKTestIvfpqScan", "GammaKTestIvfflatScan", "GammaKTestPqTablesA",
+    "GammaKTestPqTablesB", "GammaKTestPqCwn", "GammaKTestPqSterm",
+    "GammaKTestPqStermBuckets", "GammaKTestBucketScatter",
+    "GammaKTestResiduals", "GammaKTestRowNorms", "GammaKTestExtractProbe0",
+    "GammaKTestRabitqSvalBuckets",
 ]
 
 F32 = np.finfo(np.float32)
@@ -165,6 +170,86 @@ def test_pq_encode_ref_ties_to_lowest_and_pack4():
     assert p.shape == (50, 1)
     assert np.array_equal(p[:, 0] & 15, codes[:, 0])
     assert np.array_equal(p[:, 0] >> 4, codes[:, 1])
+
+
+def _f32(x):
+    """round a Python float to fp32 (struct does IEEE round-to-nearest)"""
+    import struct
+    return struct.unpack("f", struct.pack("f", x))[0]
+
+
+def test_unpack4_inverts_pack4():
+    rng = np.random.default_rng(3)
+    codes = rng.integers(0, 16, size=(37, 12), dtype=np.uint8)
+    p = kr.pack4(codes)
+    assert p.shape == (37, 6)
+    assert np.array_equal(kr.unpack4(p), codes)
+    assert kr.unpack4(np.array([[0xA3]], np.uint8)).tolist() == [[3, 10]]
+
+
+def test_adc_chain_and_sterm_ref_round_after_every_add():
+    """Against a Python loop that rounds to fp32 after each add, on
+    Gaussian tables where the order of the adds shows in the bits."""
+    rng = np.random.default_rng(11)
+    M, ksub, nlist, n = 12, 16, 3, 40
+    btab = rng.standard_normal((nlist, M, ksub)).astype(np.float32)
+    codes = rng.integers(0, ksub, size=(n, M), dtype=np.uint8)
+    start = rng.standard_normal(n).astype(np.float32)
+    got = kr.adc_chain(start, btab[1], codes)
+    assert got.dtype == np.float32
+    for i in range(n):
+        acc = float(start[i])
+        for m in range(M):
+            acc = _f32(acc + float(btab[1, m, codes[i, m]]))
+        assert got[i] == acc
+    # the chain is order-sensitive here: descending m gives other bits
+    rev = kr.adc_chain(start, btab[1][::-1], codes[:, ::-1])
+    assert not np.array_equal(got, rev)
+    # a scalar start broadcasts
+    s0 = kr.adc_chain(np.float32(0.5), btab[0], codes)
+    assert np.array_equal(
+        s0, kr.adc_chain(np.full(n, 0.5, np.float32), btab[0], codes))
+    asg = rng.integers(0, nlist, size=n).astype(np.int32)
+    asg[[0, 7]] = -1
+    asg[[3, 9]] = nlist
+    sv = kr.sterm_ref(btab, codes, asg)
+    for i in range(n):
+        if not 0 <= asg[i] < nlist:
+            assert sv[i] == 0.0
+            continue
+        acc = 0.0
+        for m in range(M):
+            acc = _f32(acc + float(btab[asg[i], m, codes[i, m]]))
+        assert sv[i] == acc
+
+
+def test_oracle_chain_wrappers():
+    """The array wrappers over the oracle library's serial-fmaf chains:
+    shapes, the zero-query identity the pq_cwn reference rests on, and a
+    float64 cross-check on grid inputs, where every chain is exact."""
+    from oracle import gamma_oracle as go
+    d, M, ksub = 24, 4, 16
+    q, cent = kr.grid((3, d), 1), kr.grid((5, d), 2)
+    cb = kr.grid((M, ksub, d // M), 3)
+    a = go.pct1_a_table(q, cb, M, ksub)
+    b = go.pct1_b_table(cent, cb, M, ksub)
+    t = go.adc_table_ip(q, cb, M, ksub)
+    assert a.shape == t.shape == (3, M, ksub) and b.shape == (5, M, ksub)
+    cb64 = cb.astype(np.float64)
+    dots = np.einsum("qmt,mjt->qmj", q.reshape(3, M, -1).astype(np.float64),
+                     cb64)
+    cwn = (cb64 * cb64).sum(axis=2)
+    assert np.array_equal(t, dots)
+    assert np.array_equal(a, cwn[None] - 2.0 * dots)
+    assert np.array_equal(b, 2.0 * np.einsum(
+        "lmt,mjt->lmj", cent.reshape(5, M, -1).astype(np.float64), cb64))
+    # zero query: fmaf(-2, 0, cwn) == cwn exactly, also off the grid
+    g = np.random.default_rng(4).standard_normal(
+        (M, ksub, d // M)).astype(np.float32)
+    z = go.pct1_a_table(np.zeros((1, d), np.float32), g, M, ksub)[0]
+    n2 = go.ip_serial(g.reshape(-1, d // M)[:5], g.reshape(-1, d // M)[:5])
+    assert np.array_equal(z.ravel()[:5], np.diag(n2))
+    assert np.array_equal(go.ip_serial(q, cent), kr.dots_exact(q, cent))
 
 
 def test_libgamma_exports_kernel_test_hooks():

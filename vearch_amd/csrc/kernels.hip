@@ -766,11 +766,20 @@ k_ivfpq_scan(int nq, int S, int d, int M, int nprobe, int k2,
       sel.maybe_flush(fmargin);
     }
   } else {
-    for (int p = sub; p < nprobe; p += S) {
-      if (kill_flag &&
-          __hip_atomic_load(kill_flag, __ATOMIC_RELAXED,
-                            __HIP_MEMORY_SCOPE_AGENT))
-        break;
+    int kslot = 0;
+    for (int p = sub; p < nprobe; p += S, kslot ^= 1) {
+      if (kill_flag) {
+        /* one thread polls the kill flag and the block reads its answer
+         * from LDS behind a barrier, so every thread leaves at the same
+         * probe even when the flag flips between two threads' reads. The
+         * slots alternate: one is rewritten two barriers after it was
+         * read. */
+        if (threadIdx.x == 0)
+          ch->kill[kslot] = __hip_atomic_load(kill_flag, __ATOMIC_RELAXED,
+                                              __HIP_MEMORY_SCOPE_AGENT);
+        __syncthreads();
+        if (ch->kill[kslot]) break;
+      }
       int64_t ln = probes[(int64_t)q * nprobe + p];
       if (ln < 0 || ln >= nlist) continue;
       GammaBucketDev bk = buckets[ln];
@@ -1162,7 +1171,8 @@ k_ivfpq_scan4(int nq, int S, int d, int M, int nprobe, int k2,
   float *qs = (float *)(res + k2);                  /* d (IP table build) */
   float *dis0s = qs + d;                            /* 2 (one per half) */
   long long *szsh = (long long *)(dis0s + 2);       /* 2 (list sizes) */
-  int *state = (int *)(szsh + 2) + 1;               /* int[2] */
+  int *state = (int *)(szsh + 2) + 1;               /* int[1] */
+  int *killsh = state + 1;                          /* int[2] */
 
   const int bq = blockIdx.x / S;
   const int sub = blockIdx.x - bq * S;
@@ -1201,10 +1211,12 @@ k_ivfpq_scan4(int nq, int S, int d, int M, int nprobe, int k2,
     for (int t = 0;; t += 2) {
       int p0 = sub + t * S;
       if (p0 >= nprobe) break;
-      if (kill_flag &&
-          __hip_atomic_load(kill_flag, __ATOMIC_RELAXED,
-                            __HIP_MEMORY_SCOPE_AGENT))
-        break;
+      /* one thread polls the kill flag; the block reads its answer from
+       * LDS behind the barrier below, so every thread leaves at the same
+       * pair even when the flag flips between two threads' reads */
+      if (kill_flag && threadIdx.x == 0)
+        killsh[0] = __hip_atomic_load(kill_flag, __ATOMIC_RELAXED,
+                                      __HIP_MEMORY_SCOPE_AGENT);
       int p = sub + (t + half) * S;
       int64_t ln = -1;
       if (p < nprobe) ln = probes[(int64_t)q * nprobe + p];
@@ -1229,6 +1241,7 @@ k_ivfpq_scan4(int nq, int S, int d, int M, int nprobe, int k2,
         if (tid == 0) szsh[half] = bk.size;
       }
       __syncthreads();
+      if (kill_flag && killsh[0]) break;
       if (IP) dis0 = dis0s[half];
       long long maxsz = szsh[0] > szsh[1] ? szsh[0] : szsh[1];
       const uint32_t *ids = bk.ids;
@@ -1273,14 +1286,20 @@ k_ivfpq_scan4(int nq, int S, int d, int M, int nprobe, int k2,
         }
         sel.maybe_flush(blockDim.x * C);
       }
-      __syncthreads(); /* dis0s/szsh rewritten next pair */
+      __syncthreads(); /* dis0s/szsh/killsh rewritten next pair */
     }
   } else {
-    for (int p = sub; p < nprobe; p += S) {
-      if (kill_flag &&
-          __hip_atomic_load(kill_flag, __ATOMIC_RELAXED,
-                            __HIP_MEMORY_SCOPE_AGENT))
-        break;
+    int kslot = 0;
+    for (int p = sub; p < nprobe; p += S, kslot ^= 1) {
+      if (kill_flag) {
+        /* block-uniform poll, as in the fast path. The slots alternate:
+         * one is rewritten two barriers after it was read. */
+        if (threadIdx.x == 0)
+          killsh[kslot] = __hip_atomic_load(kill_flag, __ATOMIC_RELAXED,
+                                            __HIP_MEMORY_SCOPE_AGENT);
+        __syncthreads();
+        if (killsh[kslot]) break;
+      }
       int64_t ln = probes[(int64_t)q * nprobe + p];
       if (ln < 0 || ln >= nlist) continue;
       GammaBucketDev bk = buckets[ln];

@@ -142,6 +142,60 @@ int GammaKTestIvfpqWideInfo(int d, int M, int ksub, int k2, int *out5) {
   return 0;
 }
 
+int GammaKTestIvfflatScan(int nq, int d, int nprobe, int k2,
+                          const float *queries, const void *buckets_dev,
+                          int nlist, const int64_t *probes,
+                          const uint32_t *bitmap, int ip,
+                          uint64_t *out_keys) {
+  return kt_done(gk::ivfflat_scan(nullptr, nq, d, nprobe, k2, queries,
+                                  (const GammaBucketDev *)buckets_dev, nlist,
+                                  probes, bitmap, ip != 0, out_keys));
+}
+
+int GammaKTestPqTablesB(int d, int M, int ksub, int nlist,
+                        const float *centroids, const float *codebooks,
+                        float *btab) {
+  return kt_done(gk::pq_tables_b(nullptr, d, M, ksub, nlist, centroids,
+                                 codebooks, btab));
+}
+
+int GammaKTestPqSterm(int64_t n, int M, int ksub, int nlist,
+                      const uint8_t *codes, const int32_t *asg, int asg_const,
+                      const float *btab, float *out) {
+  return kt_done(gk::pq_sterm(nullptr, n, M, ksub, nlist, codes, asg,
+                              asg_const, btab, out));
+}
+
+int GammaKTestPqStermBuckets(int nlist, int M, int ksub, const void *bks_dev,
+                             const float *btab) {
+  return kt_done(gk::pq_sterm_buckets(nullptr, nlist, M, ksub,
+                                      (const GammaBucketDev *)bks_dev, btab));
+}
+
+int GammaKTestBucketScatter(int nseg, const void *segs_dev,
+                            const uint32_t *ids_src, const uint8_t *data_src,
+                            const float *svals_src, int entry_bytes) {
+  static_assert(sizeof(GammaScatterSeg) == 40, "5 x 8-byte fields");
+  return kt_done(gk::bucket_scatter(nullptr, nseg,
+                                    (const GammaScatterSeg *)segs_dev, ids_src,
+                                    data_src, svals_src, entry_bytes));
+}
+
+int GammaKTestResiduals(int64_t n, int d, const float *x,
+                        const float *centroids, const int32_t *assign,
+                        float *out) {
+  return kt_done(gk::residuals(nullptr, n, d, x, centroids, assign, out));
+}
+
+int GammaKTestRowNorms(const float *v, int64_t n, int d, float *norms) {
+  return kt_done(gk::row_norms(nullptr, v, n, d, norms));
+}
+
+int GammaKTestExtractProbe0(int nq, int nprobe, const int64_t *probes,
+                            int32_t *out) {
+  return kt_done(gk::extract_probe0(nullptr, nq, nprobe, probes, out));
+}
+
 int GammaKTestHammingMatrix(const uint32_t *Q, int nq, const uint32_t *B,
                             int64_t n, int W, float *out) {
   return kt_done(gk::hamming_matrix(nullptr, Q, nq, B, n, W, out));
@@ -183,6 +237,13 @@ int GammaKTestRabitqScan(int nq, int S, int d, int nprobe, int k2,
                                  (const GammaBucketDev *)buckets_dev, nlist,
                                  probes, bitmap, ip != 0, out_keys,
                                  kill_flag));
+}
+
+int GammaKTestRabitqSvalBuckets(int nlist, int d, const void *bks_dev,
+                                const float *centroids) {
+  return kt_done(gk::rabitq_sval_buckets(nullptr, nlist, d,
+                                         (const GammaBucketDev *)bks_dev,
+                                         centroids));
 }
 
 } /* extern "C" */

@@ -62,6 +62,17 @@ def _lib():
             i64, i32, vp, vp, i32, i32, vp, i32, vp, vp]
         L.GammaKTestRabitqScan.argtypes = [
             i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp]
+        L.GammaKTestIvfflatScan.argtypes = [
+            i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp]
+        L.GammaKTestPqTablesB.argtypes = [i32, i32, i32, i32, vp, vp, vp]
+        L.GammaKTestPqSterm.argtypes = [
+            i64, i32, i32, i32, vp, vp, i32, vp, vp]
+        L.GammaKTestPqStermBuckets.argtypes = [i32, i32, i32, vp, vp]
+        L.GammaKTestBucketScatter.argtypes = [i32, vp, vp, vp, vp, i32]
+        L.GammaKTestResiduals.argtypes = [i64, i32, vp, vp, vp, vp]
+        L.GammaKTestRowNorms.argtypes = [vp, i64, i32, vp]
+        L.GammaKTestExtractProbe0.argtypes = [i32, i32, vp, vp]
+        L.GammaKTestRabitqSvalBuckets.argtypes = [i32, i32, vp, vp]
         _ready = True
     return L
 
@@ -396,8 +407,9 @@ def ivfpq_scan_reads_table(d, M, k2, ip, ksub=256):
 
 def ivfpq_scan(lists, probes, probe_dists, queries, centroids, codebooks,
                S, k2, ip, bitmap=None, qmap=None, kill_flag=None,
-               code_offsets=None):
-    """One gk::ivfpq_scan launch (8-bit codes) on host arrays.
+               code_offsets=None, ksub=256):
+    """One gk::ivfpq_scan launch on host arrays (8-bit codes; ksub=16: the
+    4-bit kernel, see the end of this text).
     lists: one (ids uint32 (n,), codes uint8 (n, M), svals float32 (n,))
     per inverted list, n = that list's size (0 is legal); every array gets
     its own device allocation. probes int64 (nq, nprobe) may hold -1 and
@@ -408,6 +420,12 @@ def ivfpq_scan(lists, probes, probe_dists, queries, centroids, codebooks,
     flag raised before the launch). code_offsets: optional {list index:
     byte offset (a multiple of 4)}: that list's codes start this far into
     their allocation, so they are 4-byte but not 16-byte aligned.
+    ksub=16: codebooks are (M, 16, d/M); a list's codes arrive as (n, M)
+    values below 16 and are packed into (n, M/2) bucket bytes (low nibble =
+    even sub-quantizer); the L2 table is pq_tables_a at ksub 16, inner
+    product passes no table (the kernel builds its own) and cwn is NULL;
+    code_offsets is refused: the fast shapes load 8- and 16-byte vectors and
+    rely on the buckets' alignment.
     Returns (keys, dists, ids): keys uint64 (nq, S, k2) as the kernel
     wrote them, and the merge the engine applies to the S partial rows of
     a query (gk::sort_rows over S*k2 keys), top-k2: dists float32 and ids
@@ -419,8 +437,14 @@ def ivfpq_scan(lists, probes, probe_dists, queries, centroids, codebooks,
     nq, d = q_d.shape
     nlist = len(lists)
     M = cb_d.shape[0]
-    assert cb_d.shape[1] == 256 and cb_d.numel() == 256 * d
+    assert ksub in (16, 256)
+    assert cb_d.shape[1] == ksub and cb_d.numel() == ksub * d
     assert cent_d.shape == (nlist, d)
+    if ksub == 16:
+        from oracle.kernel_refs import pack4
+        assert not code_offsets, "4-bit entries rely on bucket alignment"
+        assert M % 2 == 0
+    eb = M if ksub == 256 else M // 2  # bytes per bucket entry
     probes = np.ascontiguousarray(probes, dtype=np.int64)
     nprobe = probes.shape[1]
     assert probes.shape == (nq, nprobe)
@@ -432,11 +456,14 @@ def ivfpq_scan(lists, probes, probe_dists, queries, centroids, codebooks,
         ids = np.ascontiguousarray(ids, dtype=np.uint32)
         n = ids.shape[0]
         codes = np.ascontiguousarray(codes, dtype=np.uint8).reshape(n, M)
+        if ksub == 16:
+            assert n == 0 or codes.max() < 16
+            codes = pack4(codes)
         svals = np.ascontiguousarray(svals, dtype=np.float32)
         assert svals.shape == (n,)
         off = (code_offsets or {}).get(li, 0)
         assert off % 4 == 0 and off >= 0
-        buf = np.full(off + n * M, 0xEE, dtype=np.uint8)
+        buf = np.full(off + n * eb, 0xEE, dtype=np.uint8)
         buf[off:] = codes.ravel()
         cbuf = torch.from_numpy(buf).cuda()
         t = [torch.from_numpy(ids.view(np.int32).copy()).cuda(),
@@ -451,14 +478,18 @@ def ivfpq_scan(lists, probes, probe_dists, queries, centroids, codebooks,
             np.ascontiguousarray(qmap, dtype=np.int32).copy()).cuda()
     # the resident-table kernels build their own IP table and ignore atab;
     # the sliced-table kernel reads it for both metrics
-    atab = pq_tables_ip(q_d, cb_d, M) if ip \
-        else pq_tables_a(q_d, cb_d, M, 256)
-    cwn = pq_cwn(cb_d, M, 256)
+    if ksub == 256:
+        atab = pq_tables_ip(q_d, cb_d, M) if ip \
+            else pq_tables_a(q_d, cb_d, M, 256)
+        cwn = pq_cwn(cb_d, M, 256)
+    else:
+        atab = None if ip else pq_tables_a(q_d, cb_d, M, 16)
+        cwn = None
     kf_d = None if kill_flag is None else torch.full(
         (1,), int(kill_flag), dtype=torch.int32, device="cuda")
     keys = torch.full((nq, S, k2), 0x5A5A5A5A5A5A5A5A, dtype=torch.int64,
                       device="cuda")
-    _call("GammaKTestIvfpqScan", nq, S, d, M, 256, nprobe, k2, _p(q_d),
+    _call("GammaKTestIvfpqScan", nq, S, d, M, ksub, nprobe, k2, _p(q_d),
           _p(cent_d), _p(cb_d), _p(atab), _p(cwn), _p(pd_d),
           _p(bk_d, torch.int64), nlist, _p(pr_d, torch.int64),
           _p(bm_d, torch.int32), int(bool(ip)), _p(keys, torch.int64),
@@ -467,6 +498,212 @@ def ivfpq_scan(lists, probes, probe_dists, queries, centroids, codebooks,
         return keys_to_np(keys), None, None
     od, oi = sort_rows(keys.reshape(nq, S * k2), k2, ip)
     return keys_to_np(keys), od.cpu().numpy(), oi.cpu().numpy()
+
+
+def ivfflat_scan(lists, probes, queries, k2, ip, bitmap=None):
+    """One gk::ivfflat_scan launch on host arrays. lists: one (ids uint32
+    (n,), vecs float32 (n, d)) per inverted list (n = 0 is legal), each
+    array in its own device allocation; probes int64 (nq, nprobe) may hold
+    -1 and ids >= nlist; queries float32 (nq, d); bitmap: optional uint32
+    words. Returns the keys uint64 (nq, k2) as the kernel wrote them."""
+    q_d = _f32_dev(queries)
+    nq, d = q_d.shape
+    assert d % 4 == 0
+    probes = np.ascontiguousarray(probes, dtype=np.int64)
+    nprobe = probes.shape[1]
+    assert probes.shape == (nq, nprobe)
+    pr_d = torch.from_numpy(probes.copy()).cuda()
+    keep, rows = [], []
+    for ids, vecs in lists:
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        n = ids.shape[0]
+        vecs = np.ascontiguousarray(vecs, dtype=np.float32).reshape(n, d)
+        t = [torch.from_numpy(ids.view(np.int32).copy()).cuda(),
+             torch.from_numpy(vecs.copy()).cuda()]
+        keep += t
+        rows.append([x.data_ptr() if n else 0 for x in t] + [0, n])
+    bk_d = torch.tensor(rows, dtype=torch.int64).reshape(-1, 4).cuda()
+    bm_d = None if bitmap is None else bitmap_to_dev(bitmap)
+    keys = torch.full((nq, k2), 0x5A5A5A5A5A5A5A5A, dtype=torch.int64,
+                      device="cuda")
+    _call("GammaKTestIvfflatScan", nq, d, nprobe, k2, _p(q_d),
+          _p(bk_d, torch.int64), len(lists), _p(pr_d, torch.int64),
+          _p(bm_d, torch.int32), int(bool(ip)), _p(keys, torch.int64))
+    return keys_to_np(keys)
+
+
+# ------------------------------------------------- ingest and table kernels
+def _f32_dev(a):
+    return torch.from_numpy(
+        np.ascontiguousarray(a, dtype=np.float32).copy()).cuda()
+
+
+def _u8_dev(a):
+    return torch.from_numpy(
+        np.ascontiguousarray(a, dtype=np.uint8).copy()).cuda()
+
+
+def _i32_dev(a):
+    return torch.from_numpy(
+        np.ascontiguousarray(a, dtype=np.int32).copy()).cuda()
+
+
+def pq_tables_b(centroids, codebooks, M, ksub):
+    """gk::pq_tables_b on host arrays: centroids (nlist, d), codebooks
+    (M, ksub, d/M) -> btab float32 (nlist, M, ksub) numpy."""
+    c_d, cb_d = _f32_dev(centroids), _f32_dev(codebooks)
+    nlist, d = c_d.shape
+    assert ksub in (16, 256) and d % M == 0 and cb_d.numel() == ksub * d
+    btab = torch.full((nlist, M, ksub), float("nan"), dtype=torch.float32,
+                      device="cuda")
+    _call("GammaKTestPqTablesB", d, M, ksub, nlist, _p(c_d), _p(cb_d),
+          _p(btab))
+    return btab.cpu().numpy()
+
+
+def pq_sterm(codes, btab, M, ksub, asg=None, asg_const=0):
+    """gk::pq_sterm on host arrays: codes uint8 bucket entries (n, M) or, at
+    ksub = 16, packed (n, M/2); btab float32 (nlist, M, ksub); asg int32
+    (n,) list numbers (any value; outside [0, nlist) gives 0.0f) or None
+    (every vector in list asg_const). -> float32 (n,) numpy, nan where the
+    kernel wrote nothing."""
+    b_d = _f32_dev(btab)
+    nlist = b_d.shape[0]
+    assert b_d.shape == (nlist, M, ksub) and ksub in (16, 256)
+    codes = np.ascontiguousarray(codes, dtype=np.uint8)
+    n = codes.shape[0]
+    assert codes.shape == (n, M if ksub == 256 else M // 2)
+    c_d = _u8_dev(codes)
+    a_d = None if asg is None else _i32_dev(asg)
+    assert a_d is None or a_d.shape == (n,)
+    assert a_d is not None or 0 <= asg_const < nlist
+    out = torch.full((n,), float("nan"), dtype=torch.float32, device="cuda")
+    _call("GammaKTestPqSterm", n, M, ksub, nlist, _p(c_d),
+          _p(a_d, torch.int32), asg_const, _p(b_d), _p(out))
+    return out.cpu().numpy()
+
+
+SVAL_CANARY = -7.0
+
+
+def _sval_buckets(hook, buckets, entry_bytes, skip, *args):
+    """shared by pq_sterm_buckets / rabitq_sval_buckets: one (n,
+    entry_bytes) uint8 host array per bucket, each in its own allocation;
+    every svals array is n + 8 floats pre-filled with SVAL_CANARY (the
+    kernel owns the first n); buckets listed in `skip` pass svals = NULL.
+    Returns the full svals arrays (None for a skipped bucket)."""
+    keep, rows, outs = [], [], []
+    for li, ent in enumerate(buckets):
+        ent = np.ascontiguousarray(ent, dtype=np.uint8)
+        n = ent.shape[0]
+        assert ent.shape == (n, entry_bytes)
+        e_d = _u8_dev(ent)
+        sv = None if li in skip else torch.full(
+            (n + 8,), SVAL_CANARY, dtype=torch.float32, device="cuda")
+        keep += [e_d, sv]
+        rows.append([0, e_d.data_ptr() if n else 0,
+                     0 if sv is None else sv.data_ptr(), n])
+        outs.append(sv)
+    bk_d = torch.tensor(rows, dtype=torch.int64).reshape(-1, 4).cuda()
+    hook(bk_d, len(buckets), *args)
+    return [None if sv is None else sv.cpu().numpy() for sv in outs]
+
+
+def pq_sterm_buckets(buckets, btab, M, ksub, skip=()):
+    """gk::pq_sterm_buckets: bucket li's entries are scored against
+    btab[li]. See _sval_buckets for the arguments and the result."""
+    b_d = _f32_dev(btab)
+    assert b_d.shape == (len(buckets), M, ksub) and ksub in (16, 256)
+
+    def hook(bk_d, nlist):
+        _call("GammaKTestPqStermBuckets", nlist, M, ksub,
+              _p(bk_d, torch.int64), _p(b_d))
+    return _sval_buckets(hook, buckets, M if ksub == 256 else M // 2, skip)
+
+
+def rabitq_sval_buckets(buckets, centroids, skip=()):
+    """gk::rabitq_sval_buckets: bucket li holds entries of d/8 + 8 bytes of
+    list li, centroids float32 (nlist, d). See _sval_buckets."""
+    c_d = _f32_dev(centroids)
+    nlist, d = c_d.shape
+    assert nlist == len(buckets) and d % 32 == 0
+
+    def hook(bk_d, nl):
+        _call("GammaKTestRabitqSvalBuckets", nl, d, _p(bk_d, torch.int64),
+              _p(c_d))
+    return _sval_buckets(hook, buckets, d // 8 + 8, skip)
+
+
+def bucket_scatter(ids_src, data_src, svals_src, segments, entry_bytes,
+                   tail=4):
+    """One gk::bucket_scatter launch. Staged host arrays: ids_src uint32
+    (n,), data_src uint8 (n, entry_bytes), svals_src float32 (n,) or None
+    (passes NULL). segments: (src_start, count, with_svals) per bucket;
+    each bucket gets its own destination arrays of count + tail entries,
+    pre-filled with the COMPACT_CANARY_* values, and with_svals False
+    passes sval_dst = NULL. Returns one (ids uint32, data uint8, svals
+    float32 or None) per segment: the FULL arrays, canary tail included."""
+    ids_src = np.ascontiguousarray(ids_src, dtype=np.uint32)
+    n = ids_src.shape[0]
+    data_src = np.ascontiguousarray(data_src, dtype=np.uint8)
+    assert data_src.shape == (n, entry_bytes)
+    i_d = torch.from_numpy(ids_src.view(np.int32).copy()).cuda()
+    d_d = _u8_dev(data_src)
+    s_d = None if svals_src is None else _f32_dev(svals_src)
+    assert s_d is None or s_d.shape == (n,)
+    rows, outs = [], []
+    for start, count, with_sv in segments:
+        assert 0 <= start and start + count <= n
+        ids_o = torch.full((count + tail,), COMPACT_CANARY_ID,
+                           dtype=torch.int32, device="cuda")
+        data_o = torch.full((count + tail, entry_bytes), COMPACT_CANARY_BYTE,
+                            dtype=torch.uint8, device="cuda")
+        sv_o = torch.full((count + tail,), COMPACT_CANARY_SVAL,
+                          dtype=torch.float32, device="cuda") \
+            if with_sv else None
+        rows.append([ids_o.data_ptr(), data_o.data_ptr(),
+                     0 if sv_o is None else sv_o.data_ptr(), start, count])
+        outs.append((ids_o, data_o, sv_o))
+    segs = torch.tensor(rows, dtype=torch.int64).reshape(-1, 5).cuda()
+    _call("GammaKTestBucketScatter", len(segments), _p(segs, torch.int64),
+          _p(i_d, torch.int32), _p(d_d, torch.uint8),
+          _p(s_d, torch.float32), entry_bytes)
+    return [(i_o.cpu().numpy().view(np.uint32), d_o.cpu().numpy(),
+             None if s_o is None else s_o.cpu().numpy())
+            for i_o, d_o, s_o in outs]
+
+
+def residuals(x, centroids, assign):
+    """gk::residuals on host arrays -> float32 (n, d) numpy."""
+    x_d, c_d, a_d = _f32_dev(x), _f32_dev(centroids), _i32_dev(assign)
+    n, d = x_d.shape
+    assert c_d.shape[1] == d and a_d.shape == (n,)
+    assert int(a_d.min()) >= 0 and int(a_d.max()) < c_d.shape[0]
+    out = torch.full((n, d), float("nan"), dtype=torch.float32,
+                     device="cuda")
+    _call("GammaKTestResiduals", n, d, _p(x_d), _p(c_d),
+          _p(a_d, torch.int32), _p(out))
+    return out.cpu().numpy()
+
+
+def row_norms(v):
+    """gk::row_norms on a host array (n, d) -> float32 (n,) numpy."""
+    v_d = _f32_dev(v)
+    n, d = v_d.shape
+    out = torch.full((n,), float("nan"), dtype=torch.float32, device="cuda")
+    _call("GammaKTestRowNorms", _p(v_d), n, d, _p(out))
+    return out.cpu().numpy()
+
+
+def extract_probe0(probes):
+    """gk::extract_probe0 on a host int64 (nq, nprobe) -> int32 (nq,)."""
+    probes = np.ascontiguousarray(probes, dtype=np.int64)
+    nq, nprobe = probes.shape
+    p_d = torch.from_numpy(probes.copy()).cuda()
+    out = torch.full((nq,), -7, dtype=torch.int32, device="cuda")
+    _call("GammaKTestExtractProbe0", nq, nprobe, _p(p_d, torch.int64),
+          _p(out))
+    return out.cpu().numpy()
 
 
 # ------------------------------------------------------------ BINARYIVF
