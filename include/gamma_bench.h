@@ -79,8 +79,16 @@ int64_t GammaDebugNumDocs(void *engine);
 
 /* Timing of the last GammaRawSearch, in microseconds, split by stage:
  * [0]=H2D, [1]=coarse assign+select, [2]=list scan (the dominant kernel),
- * [3]=rerank+merge, [4]=D2H, [5]=total wall. Returns 0. */
+ * [3]=rerank+merge, [4]=D2H, [5]=total wall. Returns 0.
+ * Where the scan kernel re-ranked and selected the final top-k itself
+ * (below), [2] covers that fused kernel and [3] is ~0. */
 int GammaLastSearchTiming(void *engine, double *us6);
+
+/* Debug: 1 if the last GammaRawSearch[Cached] ran the exact re-rank and
+ * the final top-k inside the IVFPQ scan kernel (8-bit resident table,
+ * one workgroup per query, rerank > 0, GAMMA_FUSE_RERANK not 0), 0 if
+ * gk::rerank / gk::sort_rows ran as kernels of their own. */
+int GammaDebugLastSearchFused(void *engine);
 
 /* Compact deleted entries out of the inverted lists (the reference does
  * this inside Update only — realtime_mem_data.cc:347-370 CompactIfNeed —
@@ -182,6 +190,29 @@ int GammaKTestIvfpqScan(int nq, int S, int d, int M, int ksub, int nprobe,
                         const int64_t *probes, const uint32_t *bitmap, int ip,
                         uint64_t *out_keys, const int *kill_flag,
                         const int32_t *qmap);
+/* gk::ivfpq_scan with its re-rank block (kernels.h GammaScanRerank):
+ * with_rr != 0 passes {rr_queries (raw-space, nq x d), segs (device array
+ * of n_segs device pointers, 1 << seg_shift rows each), k, out_dists /
+ * out_ids (nq x k)} and the scan workgroups re-rank their top-k2 and write
+ * the final top-k themselves; out_keys is then not written. with_rr == 0
+ * passes no block: GammaKTestIvfpqScan. A launch that cannot fuse (S > 1,
+ * 4-bit, wide, ...) with the block set returns hipErrorInvalidValue and
+ * launches nothing. IvfpqScanCanFuseRerank is the launcher's predicate
+ * (1 / 0) under the current GAMMA_FUSE_RERANK. */
+int GammaKTestIvfpqScanRerank(int nq, int S, int d, int M, int ksub,
+                              int nprobe, int k2, const float *queries,
+                              const float *centroids, const float *codebooks,
+                              const float *atab, const float *cwn,
+                              const float *probe_dists,
+                              const void *buckets_dev, int nlist,
+                              const int64_t *probes, const uint32_t *bitmap,
+                              int ip, uint64_t *out_keys,
+                              const int *kill_flag, const int32_t *qmap,
+                              int with_rr, const float *rr_queries,
+                              const float *const *segs, int n_segs,
+                              int seg_shift, int k, float *out_dists,
+                              int64_t *out_ids);
+int GammaKTestIvfpqScanCanFuseRerank(int d, int M, int ksub, int k2, int S);
 /* The sliced-table scan (k_ivfpq_scan_wide, kernels.h "Wide tables") reads
  * atab for both metrics: PqTablesIp is gk::pq_tables_ip, the inner-product
  * table (nq x M x 256). IvfpqWideInfo: out5 = {sub-quantizers per table

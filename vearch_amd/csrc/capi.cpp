@@ -1021,6 +1021,11 @@ int GammaLastSearchTiming(void *engine, double *us6) {
   return 0;
 }
 
+int GammaDebugLastSearchFused(void *engine) {
+  if (!engine) return -1;
+  return static_cast<Engine *>(engine)->last_fused_rerank.load() ? 1 : 0;
+}
+
 int GammaCompact(void *engine, float min_ratio, int64_t *stats2) {
   if (!engine) return -1;
   int64_t st[2] = {0, 0};

@@ -1450,7 +1450,9 @@ int IVFIndex::search(const float *q_dev, int nq, int k2, int nprobe,
                      hipStream_t s, uint64_t *out_keys_dev,
                      const float *q_norms_dev, double *t_assign_ms,
                      double *t_scan_ms, SearchScratch &sc, int S,
-                     const int *kill_flag_dev) {
+                     const int *kill_flag_dev, const GammaScanRerank *rr,
+                     bool *fused) {
+  if (fused) *fused = false;
   if (!trained_) return -1;
   nprobe = std::min(nprobe, nlist_);
   if (nprobe > 1024) nprobe = 1024; /* selector cap (select.hpp) */
@@ -1537,9 +1539,21 @@ int IVFIndex::search(const float *q_dev, int nq, int k2, int nprobe,
                                  s));
       qmap_dev = sc.qmap.as<int32_t>();
     }
+    /* the fused epilogue, by the launcher's own rule; a group is a row
+     * range of the re-rank block's arrays too */
+    const bool fuse =
+        rr && fused && gk::ivfpq_scan_can_fuse_rerank(d_, M_, ksub_, k2, S);
+    if (fuse) *fused = true;
     for (int g0 = 0; g0 < nq; g0 += gq) {
       const int gn = std::min(gq, nq - g0);
       const float *qg = q_dev + (size_t)g0 * d_;
+      GammaScanRerank rg;
+      if (fuse) {
+        rg = *rr;
+        rg.queries += (size_t)g0 * d_;
+        rg.out_dists += (size_t)g0 * rr->k;
+        rg.out_ids += (size_t)g0 * rr->k;
+      }
       const float *atab = nullptr;
       if (reads_tab) {
         if (metric_ip)
@@ -1559,7 +1573,7 @@ int IVFIndex::search(const float *q_dev, int nq, int k2, int nprobe,
           dev_buckets_.as<GammaBucketDev>(), nlist_,
           sc.probes.as<int64_t>() + (size_t)g0 * nprobe, bitmap_dev,
           metric_ip, out_keys_dev + (size_t)g0 * S * k2, kill_flag_dev,
-          qmap_dev));
+          qmap_dev, fuse ? &rg : nullptr));
     }
   } else if (rabitq()) {
     /* the factor A in the entries was encoded for the table's metric; a

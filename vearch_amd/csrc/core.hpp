@@ -323,11 +323,18 @@ class IVFIndex {
   /* search: writes keys (nq x k2) into out_keys (device) */
   /* S = probe-split (out_keys must hold nq*S*k2 keys); see
    * probe_split() for the small-batch policy */
+  /* rr: the caller wants the canonical re-rank of the top-k2 and the
+   * final top-k (rr->queries = q_dev, the raw-space rows; outputs nq x
+   * rr->k). Where gk::ivfpq_scan_can_fuse_rerank allows, the IVFPQ scan
+   * does both in its own workgroups: *fused = true, rr->out_* are
+   * written and out_keys_dev is not. Otherwise *fused = false and the
+   * caller re-ranks and sorts out_keys_dev itself. */
   int search(const float *q_dev, int nq, int k2, int nprobe,
              const uint32_t *bitmap_dev, bool metric_ip, hipStream_t s,
              uint64_t *out_keys_dev, const float *q_norms_dev,
              double *t_assign_ms, double *t_scan_ms, SearchScratch &sc,
-             int S = 1, const int *kill_flag_dev = nullptr);
+             int S = 1, const int *kill_flag_dev = nullptr,
+             const GammaScanRerank *rr = nullptr, bool *fused = nullptr);
   int probe_split(int nq, int k2, int nprobe) const;
   int coarse_assign(const float *q_dev, int nq, int nprobe, bool ip,
                     const float *q_norms_dev, hipStream_t s,
@@ -628,6 +635,8 @@ class Engine {
   int table_dimension() const { return table_dim_; }
   bool binary() const { return params_.kind == IndexKind::BINARYIVF; }
   double last_timing[6] = {0, 0, 0, 0, 0, 0};
+  /* whether the last search() re-ranked inside the scan kernel */
+  std::atomic<bool> last_fused_rerank{false};
   int training_threshold() const { return training_threshold_; }
   std::string status_json() const;
 

@@ -891,6 +891,7 @@ int Engine::search(int nq, const float *xq, int k, int nprobe,
                   !index_ || !index_->trained();
   double t_assign = 0, t_scan = 0;
   bool need_canonical_rerank = true; /* FLAT & IVFFLAT canonicalize */
+  bool fused = false; /* re-rank + top-k done inside the scan kernel */
   if (use_flat && bin) {
     /* exact Hamming top-k over the raw store: integer distances, so no
      * margin and no canonical re-rank */
@@ -929,10 +930,22 @@ int Engine::search(int nq, const float *xq, int k, int nprobe,
       KillRegistry::inst().arm(request_id, pid, sc.kill_flag.as<int>());
       kf = sc.kill_flag.as<int>();
     }
+    /* the exact re-rank leg and the final top-k, offered to the scan
+     * kernel: where the index fuses them (IVFPQ, S == 1, 8-bit resident
+     * table — gk::ivfpq_scan_can_fuse_rerank) out_d / out_i are final
+     * when it returns and sc.keys is not used */
+    const GammaScanRerank rr = {qptr,
+                                raw_.dev_seg_table(),
+                                raw_.num_segs(),
+                                RawStore::SEG_SHIFT,
+                                k,
+                                sc.out_d.as<float>(),
+                                sc.out_i.as<int64_t>()};
     int rc_idx = index_->search(qptr, nq, k2, nprobe, bm, ip, s,
                                 sc.keys.as<uint64_t>(),
                                 sc.q_norms.as<float>(), &t_assign,
-                                &t_scan, sc, S, kf);
+                                &t_scan, sc, S, kf,
+                                rerank && !bin ? &rr : nullptr, &fused);
     if (kf) KillRegistry::inst().disarm(sc.kill_flag.as<int>());
     if (rc_idx) return -1;
     k2 = k2 * S; /* sub-block partials merge in the sort below */
@@ -946,15 +959,17 @@ int Engine::search(int nq, const float *xq, int k, int nprobe,
   tm.rec(2);
   if (KillRegistry::inst().killed(request_id, pid)) return -2;
 
-  if (need_canonical_rerank) {
-    GAMMA_CHECK(gk::rerank(s, nq, k2, dim_, qptr, raw_.dev_seg_table(),
-                           raw_.num_segs(), RawStore::SEG_SHIFT, ip,
-                           sc.keys.as<uint64_t>(),
-                           sc.keys.as<uint64_t>()));
+  if (!fused) {
+    if (need_canonical_rerank) {
+      GAMMA_CHECK(gk::rerank(s, nq, k2, dim_, qptr, raw_.dev_seg_table(),
+                             raw_.num_segs(), RawStore::SEG_SHIFT, ip,
+                             sc.keys.as<uint64_t>(),
+                             sc.keys.as<uint64_t>()));
+    }
+    GAMMA_CHECK(gk::sort_rows(s, nq, k2, k, sc.keys.as<uint64_t>(), ip,
+                              sc.out_d.as<float>(),
+                              sc.out_i.as<int64_t>()));
   }
-  GAMMA_CHECK(gk::sort_rows(s, nq, k2, k, sc.keys.as<uint64_t>(), ip,
-                            sc.out_d.as<float>(),
-                            sc.out_i.as<int64_t>()));
   tm.rec(3);
   GAMMA_CHECK(hipMemcpyAsync(out_dists, sc.out_d.get(),
                              (size_t)nq * k * 4, hipMemcpyDeviceToHost, s));
@@ -975,6 +990,7 @@ int Engine::search(int nq, const float *xq, int k, int nprobe,
     last_timing[3] = tm.ms(2, 3) * 1000.0;
     last_timing[4] = tm.ms(3, 4) * 1000.0;
     last_timing[5] = tm.ms(0, 4) * 1000.0;
+    last_fused_rerank = fused;
   }
   return 0;
 }

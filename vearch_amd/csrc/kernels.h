@@ -50,6 +50,20 @@ struct GammaCompactSeg {
   long long *kept_out; /* one count per segment */
 };
 
+/* re-rank block of gk::ivfpq_scan: with it the scan's workgroup re-ranks
+ * its own top-k2 against the raw store and writes the final top-k itself
+ * (what gk::rerank + gk::sort_rows do to out_keys). Rows are indexed by
+ * the ORIGINAL query row, as out_keys is. */
+struct GammaScanRerank {
+  const float *queries;     /* raw-space queries, nq x d (under OPQ the
+                             * scan's own `queries` are rotated ones) */
+  const float *const *segs; /* raw-store segment table */
+  int n_segs, seg_shift;
+  int k;                    /* results per query, <= 2048 */
+  float *out_dists;         /* nq x k; -1.0 where fewer than k exist */
+  int64_t *out_ids;         /* nq x k; -1 there */
+};
+
 namespace gk {
 
 /* Stable compaction of a batch of buckets in one launch, the mirror of
@@ -198,6 +212,16 @@ bool ivfpq_scan_builds_table(int M, int ksub, int k2);
  * every wide launch (both metrics, any M — a fast-path M is wide too once
  * 4*d fills the LDS), and L2 launches whose kernel builds no table */
 bool ivfpq_scan_reads_table(int d, int M, int ksub, int k2, bool ip);
+/* Fused re-rank: with `rr` set the resident-table 8-bit kernel ends in the
+ * epilogue of rerank_epilogue.hpp — exact distances of the query's top-k2
+ * in gk::rerank's own fmaf chain, one sort, top-k written to rr->out_* —
+ * and out_keys is not touched (it may be null). Results are bit-identical
+ * to ivfpq_scan + rerank + sort_rows. Legal where
+ * ivfpq_scan_can_fuse_rerank: S == 1, 8-bit codes, not a wide launch,
+ * d % 4 == 0. GAMMA_FUSE_RERANK=0, read per call, turns the predicate
+ * off. Any other launch with rr set, or rr->k outside [1, 2048], is
+ * hipErrorInvalidValue and launches nothing. */
+bool ivfpq_scan_can_fuse_rerank(int d, int M, int ksub, int k2, int S);
 hipError_t ivfpq_scan(hipStream_t s, int nq, int S, int d, int M, int ksub,
                       int nprobe,
                       int k2, const float *queries, const float *centroids,
@@ -206,7 +230,8 @@ hipError_t ivfpq_scan(hipStream_t s, int nq, int S, int d, int M, int ksub,
                       const GammaBucketDev *buckets,
                       int nlist, const int64_t *probes,
                       const uint32_t *bitmap, bool ip, uint64_t *out_keys,
-                      const int *kill_flag, const int32_t *qmap);
+                      const int *kill_flag, const int32_t *qmap,
+                      const GammaScanRerank *rr = nullptr);
 
 /* out[q] = (int32) probes[q*nprobe] (the schedule sort key) */
 hipError_t extract_probe0(hipStream_t s, int nq, int nprobe,

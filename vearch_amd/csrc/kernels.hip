@@ -15,6 +15,7 @@
 #include "kernels.h"
 #include "select.hpp"
 #include "scan_walk.hpp"
+#include "rerank_epilogue.hpp"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -557,7 +558,11 @@ struct GammaScanElem {
   bool live; /* false: the lane has no entry in this pass */
 };
 
-template <bool IP, int MW, int BS>
+/* RR: the launch carries a re-rank block and ends in the epilogue of
+ * rerank_epilogue.hpp instead of the out_keys store (S == 1 only). A
+ * template flag, not a run-time test: the RR = false instantiations keep
+ * the code they had before the epilogue existed. */
+template <bool IP, int MW, int BS, bool RR>
 __global__ void __launch_bounds__(BS)
 k_ivfpq_scan(int nq, int S, int d, int M, int nprobe, int k2,
              const float *__restrict__ queries,
@@ -571,7 +576,7 @@ k_ivfpq_scan(int nq, int S, int d, int M, int nprobe, int k2,
              const uint32_t *__restrict__ bitmap,
              uint64_t *__restrict__ out_keys,
              const int *__restrict__ kill_flag,
-             const int32_t *__restrict__ qmap) {
+             const int32_t *__restrict__ qmap, GammaScanRerank rr) {
   extern __shared__ char smem[];
   const int ksub = 256;
   const int dsub = d / M;
@@ -825,6 +830,15 @@ k_ivfpq_scan(int nq, int S, int d, int M, int nprobe, int k2,
     }
   }
   sel.finish();
+  if (RR) {
+    /* the table and the scan's query copy are dead: the epilogue stages
+     * candidate rows in the one and keeps the raw query in the other */
+    gamma_rerank_topk_epilogue<IP, BS>(
+        res, k2, sortbuf, lut, M * ksub, qs, rr.queries + (int64_t)q * d, d,
+        rr.segs, rr.seg_shift, rr.k, rr.out_dists + (int64_t)q * rr.k,
+        rr.out_ids + (int64_t)q * rr.k);
+    return;
+  }
   for (int i = threadIdx.x; i < k2; i += blockDim.x)
     out_keys[((int64_t)q * S + sub) * k2 + i] = res[i];
 }
@@ -1426,6 +1440,24 @@ bool gk::ivfpq_scan_reads_table(int d, int M, int ksub, int k2, bool ip) {
          (!ip && !gk::ivfpq_scan_builds_table(M, ksub, k2));
 }
 
+/* GAMMA_FUSE_RERANK=0 keeps re-rank and sort in kernels of their own
+ * (A/B runs of one build, and tests that compare the two paths) */
+static bool gamma_scan_fuse_rerank() {
+  const char *e = getenv("GAMMA_FUSE_RERANK");
+  return !(e && e[0] == '0' && e[1] == 0);
+}
+
+/* No rule on workgroups per CU: where a 64 KB or 96 KB table leaves a
+ * workgroup alone on its CU nothing hides its epilogue, and the fused
+ * kernel still measured faster than scan + re-rank + sort (d = 768, M = 96:
+ * profiles/README.md "Fused re-rank"). */
+bool gk::ivfpq_scan_can_fuse_rerank(int d, int M, int ksub, int k2, int S) {
+  if (!gamma_scan_fuse_rerank()) return false;
+  if (S != 1 || ksub != 256 || M <= 0 || d <= 0 || (d & 3)) return false;
+  if (k2 <= 0 || k2 > GAMMA_SEL_MAX_K) return false;
+  return !gk::ivfpq_scan_is_wide(d, M, ksub, k2);
+}
+
 hipError_t gk::ivfpq_scan(hipStream_t s, int nq, int S, int d, int M,
                           int ksub, int nprobe,
                           int k2, const float *queries,
@@ -1435,8 +1467,13 @@ hipError_t gk::ivfpq_scan(hipStream_t s, int nq, int S, int d, int M,
                           const GammaBucketDev *buckets, int nlist,
                           const int64_t *probes, const uint32_t *bitmap,
                           bool ip, uint64_t *out_keys,
-                          const int *kill_flag, const int32_t *qmap) {
+                          const int *kill_flag, const int32_t *qmap,
+                          const GammaScanRerank *rr) {
   if (ksub != 256 && ksub != 16) return hipErrorInvalidValue;
+  if (rr && (!gk::ivfpq_scan_can_fuse_rerank(d, M, ksub, k2, S) ||
+             rr->k <= 0 || rr->k > GAMMA_SORT_CAP || !rr->queries ||
+             !rr->segs || !rr->out_dists || !rr->out_ids))
+    return hipErrorInvalidValue;
   const int BS = gamma_scan_bs();
   dim3 g((uint32_t)nq * (uint32_t)S);
   if (ksub == 256 && gk::ivfpq_scan_is_wide(d, M, ksub, k2)) {
@@ -1466,11 +1503,17 @@ hipError_t gk::ivfpq_scan(hipStream_t s, int nq, int S, int d, int M,
     if (!ip && (fast ? !cwn : !atab)) return hipErrorInvalidValue;
     const size_t smem = gamma_scan8_smem(M, k2, d);
     if (smem > 160 * 1024) return hipErrorInvalidValue;
-#define GAMMA_LAUNCH_SCAN(IPV, MWV, BSV)                                  \
-  k_ivfpq_scan<IPV, MWV, BSV><<<g, dim3(BSV), smem, s>>>(                 \
+    const GammaScanRerank rr0 = {};
+#define GAMMA_LAUNCH_SCAN_RR(IPV, MWV, BSV, RRV)                          \
+  k_ivfpq_scan<IPV, MWV, BSV, RRV><<<g, dim3(BSV), smem, s>>>(            \
       nq, S, d, M, nprobe, k2, queries, centroids, codebooks, atab, cwn,  \
       probe_dists, buckets, nlist, probes, bitmap, out_keys, kill_flag,   \
-      qmap)
+      qmap, RRV ? *rr : rr0)
+#define GAMMA_LAUNCH_SCAN(IPV, MWV, BSV)                                  \
+  do {                                                                    \
+    if (rr) GAMMA_LAUNCH_SCAN_RR(IPV, MWV, BSV, true);                    \
+    else GAMMA_LAUNCH_SCAN_RR(IPV, MWV, BSV, false);                      \
+  } while (0)
 #define GAMMA_LAUNCH_SCAN_BS(IPV, MWV)                                    \
   do {                                                                    \
     if (BS == 256) GAMMA_LAUNCH_SCAN(IPV, MWV, 256);                      \
@@ -1491,6 +1534,7 @@ hipError_t gk::ivfpq_scan(hipStream_t s, int nq, int S, int d, int M,
     }
 #undef GAMMA_LAUNCH_SCAN_BS
 #undef GAMMA_LAUNCH_SCAN
+#undef GAMMA_LAUNCH_SCAN_RR
     return hipGetLastError();
   }
   /* 4-bit codes: table M*16 floats (2 KB at M=32, small next to the

@@ -128,6 +128,33 @@ int GammaKTestIvfpqScan(int nq, int S, int d, int M, int ksub, int nprobe,
                                 qmap));
 }
 
+int GammaKTestIvfpqScanRerank(int nq, int S, int d, int M, int ksub,
+                              int nprobe, int k2, const float *queries,
+                              const float *centroids, const float *codebooks,
+                              const float *atab, const float *cwn,
+                              const float *probe_dists,
+                              const void *buckets_dev, int nlist,
+                              const int64_t *probes, const uint32_t *bitmap,
+                              int ip, uint64_t *out_keys,
+                              const int *kill_flag, const int32_t *qmap,
+                              int with_rr, const float *rr_queries,
+                              const float *const *segs, int n_segs,
+                              int seg_shift, int k, float *out_dists,
+                              int64_t *out_ids) {
+  const GammaScanRerank rr = {rr_queries, segs,      n_segs, seg_shift,
+                              k,          out_dists, out_ids};
+  return kt_done(gk::ivfpq_scan(nullptr, nq, S, d, M, ksub, nprobe, k2,
+                                queries, centroids, codebooks, atab, cwn,
+                                probe_dists,
+                                (const GammaBucketDev *)buckets_dev, nlist,
+                                probes, bitmap, ip != 0, out_keys, kill_flag,
+                                qmap, with_rr ? &rr : nullptr));
+}
+
+int GammaKTestIvfpqScanCanFuseRerank(int d, int M, int ksub, int k2, int S) {
+  return gk::ivfpq_scan_can_fuse_rerank(d, M, ksub, k2, S) ? 1 : 0;
+}
+
 int GammaKTestPqTablesIp(int nq, int d, int M, const float *queries,
                          const float *codebooks, float *out) {
   return kt_done(gk::pq_tables_ip(nullptr, nq, d, M, queries, codebooks, out));

@@ -82,6 +82,7 @@ def lib():
         L.GammaDebugNumDocs.argtypes = [c.c_void_p]
         L.GammaLastSearchTiming.argtypes = [c.c_void_p,
                                             c.POINTER(c.c_double)]
+        L.GammaDebugLastSearchFused.argtypes = [c.c_void_p]
         L.GammaCompact.argtypes = [c.c_void_p, c.c_float, i64p]
         L.GammaCompactStats.argtypes = [c.c_void_p, i64p]
         L.GammaBulkAddBinary.argtypes = [c.c_void_p, c.c_char_p, c.c_int,
@@ -361,6 +362,12 @@ class GammaEngine:
              "total_us"])}
 
     # ---- debug hooks for parity tests ------------------------------
+    def debug_last_search_fused(self):
+        """True if the last raw search re-ranked and selected its final
+        top-k inside the IVFPQ scan kernel (with it scan_us of
+        last_timing() covers the fused kernel and post_us is ~0)."""
+        return lib().GammaDebugLastSearchFused(self.h) == 1
+
     def debug_coarse_assign(self, queries, nprobe):
         q = self._vecs(queries)
         nq = q.shape[0]

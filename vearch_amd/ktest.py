@@ -50,6 +50,12 @@ def _lib():
         L.GammaKTestIvfpqScan.argtypes = [
             i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp,
             i32, vp, vp, i32, vp, vp, vp]
+        L.GammaKTestIvfpqScanRerank.argtypes = [
+            i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp,
+            i32, vp, vp, i32, vp, vp, vp,
+            i32, vp, vp, i32, i32, i32, vp, vp]
+        L.GammaKTestIvfpqScanCanFuseRerank.argtypes = [
+            i32, i32, i32, i32, i32]
         L.GammaKTestPqTablesIp.argtypes = [i32, i32, i32, vp, vp, vp]
         L.GammaKTestIvfpqWideInfo.argtypes = [
             i32, i32, i32, i32, c.POINTER(c.c_int)]
@@ -431,6 +437,59 @@ def ivfpq_scan(lists, probes, probe_dists, queries, centroids, codebooks,
     a query (gk::sort_rows over S*k2 keys), top-k2: dists float32 and ids
     int64 (nq, k2), -1 / -1 where fewer than k2 candidates exist (None,
     None where S * k2 exceeds what sort_rows takes)."""
+    keys = _ivfpq_scan_launch(lists, probes, probe_dists, queries,
+                              centroids, codebooks, S, k2, ip, bitmap, qmap,
+                              kill_flag, code_offsets, ksub, None)
+    nq = keys.shape[0]
+    if S * k2 > 2048:  # beyond gk::sort_rows (the engine keeps S*k2 <= 2048)
+        return keys_to_np(keys), None, None
+    od, oi = sort_rows(keys.reshape(nq, S * k2), k2, ip)
+    return keys_to_np(keys), od.cpu().numpy(), oi.cpu().numpy()
+
+
+def ivfpq_scan_can_fuse_rerank(d, M, k2, S, ksub=256):
+    """gk::ivfpq_scan_can_fuse_rerank under the current GAMMA_FUSE_RERANK:
+    the rule the launcher and IVFIndex::search both decide by."""
+    return _lib().GammaKTestIvfpqScanCanFuseRerank(d, M, ksub, k2, S) == 1
+
+
+def ivfpq_scan_rerank(lists, probes, probe_dists, queries, centroids,
+                      codebooks, S, k2, ip, base, seg_shift, k,
+                      rr_queries=None, bitmap=None, qmap=None,
+                      kill_flag=None, ksub=256):
+    """One gk::ivfpq_scan launch WITH its re-rank block: the inputs of
+    ivfpq_scan, plus the raw store `base` (n, d) host array, cut into
+    separately allocated segments of 1 << seg_shift rows, and k. rr_queries
+    (nq, d): the raw-space queries the re-rank measures against (default:
+    `queries`; under OPQ the scan's own are rotated ones). Returns (dists
+    float32, ids int64), (nq, k), pre-filled with -7 so that a launch that
+    wrote nothing shows. A launch the launcher refuses raises KTestError."""
+    rq = queries if rr_queries is None else rr_queries
+    rr = (np.ascontiguousarray(rq, dtype=np.float32),
+          split_segments(base, seg_shift), seg_shift, k)
+    od, oi = _ivfpq_scan_launch(lists, probes, probe_dists, queries,
+                                centroids, codebooks, S, k2, ip, bitmap,
+                                qmap, kill_flag, None, ksub, rr)
+    return od.cpu().numpy(), oi.cpu().numpy()
+
+
+def ivfpq_scan_null_rerank(lists, probes, probe_dists, queries, centroids,
+                           codebooks, S, k2, ip, bitmap=None, qmap=None,
+                           kill_flag=None, ksub=256):
+    """The re-rank hook with NO block: today's launch. Returns the keys
+    uint64 (nq, S, k2) as ivfpq_scan returns them."""
+    return keys_to_np(_ivfpq_scan_launch(
+        lists, probes, probe_dists, queries, centroids, codebooks, S, k2,
+        ip, bitmap, qmap, kill_flag, None, ksub, "null"))
+
+
+def _ivfpq_scan_launch(lists, probes, probe_dists, queries, centroids,
+                       codebooks, S, k2, ip, bitmap, qmap, kill_flag,
+                       code_offsets, ksub, rr):
+    """The launch behind ivfpq_scan (rr None: returns the (nq, S, k2) key
+    tensor) and ivfpq_scan_rerank (rr = (raw queries, segments, seg_shift,
+    k): returns the (dists, ids) tensors; the key tensor is checked to be
+    untouched)."""
     f32 = lambda a: torch.from_numpy(  # noqa: E731
         np.ascontiguousarray(a, dtype=np.float32).copy()).cuda()
     q_d, cent_d, cb_d = f32(queries), f32(centroids), f32(codebooks)
@@ -489,15 +548,29 @@ def ivfpq_scan(lists, probes, probe_dists, queries, centroids, codebooks,
         (1,), int(kill_flag), dtype=torch.int32, device="cuda")
     keys = torch.full((nq, S, k2), 0x5A5A5A5A5A5A5A5A, dtype=torch.int64,
                       device="cuda")
-    _call("GammaKTestIvfpqScan", nq, S, d, M, ksub, nprobe, k2, _p(q_d),
-          _p(cent_d), _p(cb_d), _p(atab), _p(cwn), _p(pd_d),
-          _p(bk_d, torch.int64), nlist, _p(pr_d, torch.int64),
-          _p(bm_d, torch.int32), int(bool(ip)), _p(keys, torch.int64),
-          _p(kf_d, torch.int32), _p(qm_d, torch.int32))
-    if S * k2 > 2048:  # beyond gk::sort_rows (the engine keeps S*k2 <= 2048)
-        return keys_to_np(keys), None, None
-    od, oi = sort_rows(keys.reshape(nq, S * k2), k2, ip)
-    return keys_to_np(keys), od.cpu().numpy(), oi.cpu().numpy()
+    args = (nq, S, d, M, ksub, nprobe, k2, _p(q_d),
+            _p(cent_d), _p(cb_d), _p(atab), _p(cwn), _p(pd_d),
+            _p(bk_d, torch.int64), nlist, _p(pr_d, torch.int64),
+            _p(bm_d, torch.int32), int(bool(ip)), _p(keys, torch.int64),
+            _p(kf_d, torch.int32), _p(qm_d, torch.int32))
+    if rr is None:
+        _call("GammaKTestIvfpqScan", *args)
+        return keys
+    if rr == "null":  # the re-rank hook, no block: the plain launch
+        _call("GammaKTestIvfpqScanRerank", *args, 0, None, None, 0, 0, 0,
+              None, None)
+        return keys
+    rq, segs, seg_shift, k = rr
+    rq_d = f32(rq)
+    assert rq_d.shape == (nq, d)
+    table = seg_table(segs)
+    od = torch.full((nq, k), -7.0, dtype=torch.float32, device="cuda")
+    oi = torch.full((nq, k), -7, dtype=torch.int64, device="cuda")
+    _call("GammaKTestIvfpqScanRerank", *args, 1, _p(rq_d), _p(table),
+          len(segs), seg_shift, k, _p(od), _p(oi))
+    assert bool((keys == 0x5A5A5A5A5A5A5A5A).all()), \
+        "a fused launch wrote out_keys"
+    return od, oi
 
 
 def ivfflat_scan(lists, probes, queries, k2, ip, bitmap=None):
