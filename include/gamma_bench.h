@@ -291,6 +291,22 @@ int GammaKTestRabitqScan(int nq, int S, int d, int nprobe, int k2,
                          int ip, uint64_t *out_keys, const int *kill_flag);
 int GammaKTestRabitqSvalBuckets(int nlist, int d, const void *bks_dev,
                                 const float *centroids);
+/* gk::coarse_select, the seed-filtered coarse assign (kernels.h): dots is
+ * nq x nlist floats of scratch, cand nq x cap keys, cand_cnt nq + 1 ints
+ * (per-query candidate counters, then the overflow flag), sel_keys the
+ * nq x nprobe result. n1 / cap <= 0 take the knobs' values. Where
+ * CoarseCanFilter is 0 the plain full-width pair runs and cand / cand_cnt
+ * stay as they were. CoarseCanFilter returns gk::coarse_can_filter (1 / 0)
+ * under the current GAMMA_FUSE_COARSE; knobs2 (optional, host) receives
+ * {GAMMA_COARSE_SEED_COLS, GAMMA_COARSE_CAND_CAP} as read. */
+int GammaKTestCoarseSelect(const float *Q, int nq, const float *B,
+                           int64_t nlist, int d, const float *qnorms,
+                           const float *bnorms, int l2, int ip_order,
+                           int nprobe, int n1, int cap, float *dots,
+                           uint64_t *cand, int *cand_cnt,
+                           uint64_t *sel_keys);
+int GammaKTestCoarseCanFilter(int nq, int64_t nlist, int d, int nprobe,
+                              int n1, int *knobs2);
 
 #ifdef __cplusplus
 }

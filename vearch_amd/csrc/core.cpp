@@ -1397,6 +1397,22 @@ int IVFIndex::coarse_assign(const float *q_dev, int nq, int nprobe, bool ip,
   if (bin) ip = false;
   for (int64_t r0 = 0; r0 < nq; r0 += sub) {
     int64_t rn = std::min<int64_t>(sub, nq - r0);
+    if (!bin && !full_sort &&
+        gk::coarse_can_filter((int)rn, nlist_, d_, nprobe)) {
+      /* seed-filtered GEMM: the dots matrix is written for the seed
+       * columns only (and in full, device-side, if a candidate list
+       * overflowed) */
+      const int cap = gk::coarse_cand_cap();
+      if (sc.coarse_cand.reserve((size_t)rn * cap * 8)) return -1;
+      if (sc.coarse_cnt.reserve(((size_t)rn + 1) * 4)) return -1;
+      GAMMA_CHECK(gk::coarse_select(
+          s, q_dev + (size_t)r0 * d_, (int)rn, centroids_.as<float>(),
+          nlist_, d_, q_norms_dev + r0, cent_norms_.as<float>(), !ip, ip,
+          nprobe, 0, cap, sc.dots.as<float>(),
+          sc.coarse_cand.as<uint64_t>(), sc.coarse_cnt.as<int>(),
+          sc.sel_keys.as<uint64_t>() + (size_t)r0 * nprobe));
+      continue;
+    }
     if (bin)
       GAMMA_CHECK(gk::hamming_matrix(
           s, (const uint32_t *)q_dev + (size_t)r0 * d_, (int)rn,

@@ -249,6 +249,9 @@ struct SearchScratch {
   std::vector<uint32_t> filt_host;
   /* index-side (coarse assign + ADC scan) */
   DeviceBuf dots, sel_keys, probes, pdists, atab;
+  /* gk::coarse_select: candidate keys and counters + overflow flag of one
+   * query group */
+  DeviceBuf coarse_cand, coarse_cnt;
   /* cache-clustered query schedule (see kernels.h ivfpq_scan qmap) */
   DeviceBuf qcol, qmap;
   std::vector<int32_t> qcol_h, qmap_h;

@@ -87,9 +87,13 @@ hipError_t bucket_scatter(hipStream_t s, int nseg,
                           const uint8_t *data_src,
                           const float *svals_src, int entry_bytes);
 
-/* out[i*n+j] = dot(Q_i, B_j); f32 MFMA 16x16x4. */
+/* out[i*n+j] = dot(Q_i, B_j); f32 MFMA 16x16x4.
+ * run_if (optional, device): the kernel returns at entry when *run_if is
+ * 0. Only the tiled launch (nq >= 64, n >= 64) has this switch; with any
+ * other shape a non-null run_if is hipErrorInvalidValue. */
 hipError_t dots_mfma(hipStream_t s, const float *Q, int nq, const float *B,
-                     int64_t n, int d, float *out);
+                     int64_t n, int d, float *out,
+                     const int *run_if = nullptr);
 
 /* norms[i] = sum_j v[i][j]^2, canonical sequential fmaf. */
 hipError_t row_norms(hipStream_t s, const float *v, int64_t n, int d,
@@ -103,7 +107,39 @@ hipError_t select_from_dots(hipStream_t s, int nq, int64_t ncols,
                             int64_t col_base, int64_t ld, const float *dots,
                             const float *qnorms, const float *bnorms,
                             bool l2, bool ip_order, const uint32_t *bitmap,
-                            int k2, uint64_t *state_keys, bool seeded);
+                            int k2, uint64_t *state_keys, bool seeded,
+                            const int *run_if = nullptr);
+
+/* Coarse assign without the nq x nlist round trip (DESIGN.md "Kernels"
+ * (a2)): sel_keys (nq x nprobe u64, sorted) = exact top-nprobe of
+ * select_from_dots over all nlist columns of Q x B^T, bit for bit.
+ *   1. dots_mfma + select_from_dots on columns [0, n1): the seeds; the
+ *      last seed key tau_q bounds row q's nprobe-th key from above.
+ *   2. the tiled GEMM over [n1, nlist) with a filtering epilogue: a key
+ *      below tau_q is appended to cand[q] (cap slots; cand_cnt[q] keeps
+ *      counting past cap). Nothing else is written.
+ *   3. a wave per query merges seeds and candidates.
+ *   4. dots_mfma + select_from_dots on all columns, switched by the
+ *      overflow flag cand_cnt[nq] that step 3 raises when a counter ran
+ *      past cap: empty workgroups otherwise.
+ * All on stream s, no host sync. dots: nq x nlist floats; cand: nq x cap
+ * u64; cand_cnt: nq + 1 ints (counters, then the flag; zeroed here).
+ * n1 <= 0 / cap <= 0 take GAMMA_COARSE_SEED_COLS (4096) /
+ * GAMMA_COARSE_CAND_CAP (1024). Where coarse_can_filter is false this is
+ * the plain full-width pair and cand / cand_cnt are not touched. */
+hipError_t coarse_select(hipStream_t s, const float *Q, int nq,
+                         const float *B, int64_t nlist, int d,
+                         const float *qnorms, const float *bnorms, bool l2,
+                         bool ip_order, int nprobe, int n1, int cap,
+                         float *dots, uint64_t *cand, int *cand_cnt,
+                         uint64_t *sel_keys);
+/* nq >= 64, d % 4 == 0, nprobe <= 192 (the wave selector's range), n1 a
+ * multiple of 128 with nprobe <= n1 and 2 * n1 <= nlist (n1 <= 0: the
+ * knob). GAMMA_FUSE_COARSE=0, read per call, turns it off. The caller
+ * keeps binary centroids and the full-sort branch away. */
+bool coarse_can_filter(int nq, int64_t nlist, int d, int nprobe, int n1 = 0);
+int coarse_seed_cols(); /* GAMMA_COARSE_SEED_COLS, default 4096 */
+int coarse_cand_cap();  /* GAMMA_COARSE_CAND_CAP, default 1024 */
 
 /* Full-sort row select for short rows (ncols <= 8192, no bitmap):
  * one workgroup bitonic-sorts the whole row of (dist,id) keys and emits

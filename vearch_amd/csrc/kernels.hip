@@ -87,10 +87,31 @@ k_dots_mfma(const float *__restrict__ Q, int nq,
  * chain. */
 #define GT_BM 128
 #define GT_BK 32
-__global__ void __launch_bounds__(WG)
-k_dots_mfma_tiled(const float *__restrict__ Q, int nq,
-                  const float *__restrict__ B, int64_t n, int d,
-                  float *__restrict__ out) {
+
+/* Epilogue arguments of the filtered instantiation (coarse assign, see
+ * gk::coarse_select): instead of storing the tile, every accumulator
+ * becomes the select kernel's key and is appended to its query's
+ * candidate list where it is below that query's seed threshold. */
+struct GammaDotsFilter {
+  const float *qnorms;    /* [nq], read when l2 */
+  const float *bnorms;    /* indexed by the global column id, when l2 */
+  const uint64_t *thresh; /* tau of row q at thresh[q * thresh_ld] */
+  int64_t thresh_ld;
+  int64_t col_base;       /* global id of B's row 0 */
+  int l2;
+  uint64_t *cand;         /* [nq][cap] */
+  int *cand_cnt;          /* [nq], keeps counting past cap */
+  int cap;
+};
+
+/* FILTER = false: the tile is stored to `out` (fp unused). FILTER = true:
+ * fp's epilogue, nothing is stored to `out`. Tiles, k order and tail
+ * guards are the same, so a dot is the same bits in both. */
+template <bool FILTER, bool IP>
+__device__ __forceinline__ void
+gamma_dots_tile(const float *__restrict__ Q, int nq,
+                const float *__restrict__ B, int64_t n, int d,
+                float *__restrict__ out, const GammaDotsFilter &fp) {
   __shared__ float As[GT_BM][GT_BK + 1];
   __shared__ float Bs[GT_BM][GT_BK + 1];
   const int lane = threadIdx.x & 63;
@@ -147,28 +168,141 @@ k_dots_mfma_tiled(const float *__restrict__ Q, int nq,
     __syncthreads();
   }
   /* D mapping: col=lane&15, row=(lane>>4)*4+r (guide §3) */
+  if constexpr (!FILTER) {
 #pragma unroll
-  for (int fi = 0; fi < 4; fi++) {
+    for (int fi = 0; fi < 4; fi++) {
+#pragma unroll
+      for (int fj = 0; fj < 4; fj++) {
+        int64_t col = col0 + wc + fj * 16 + (lane & 15);
+        if (col >= n) continue;
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+          int qi = row0 + wr + fi * 16 + (lane >> 4) * 4 + r;
+          if (qi < nq) out[(int64_t)qi * n + col] = acc[fi][fj][r];
+        }
+      }
+    }
+  } else {
+    /* A lane holds 4 columns x 16 rows. dist is k_select_from_dots_wave's
+     * expression; key < tau is strict because ids are distinct.
+     * One global atomic per passing key made this epilogue as long as the
+     * k loop (a wave waited for ~40 returns one after the other), so
+     * slots are handed out in two levels: every row of the tile counts
+     * its passing keys in an LDS counter (a lane adds the 0..4 it holds
+     * and keeps the offset it got), one thread per row reserves that many
+     * slots of its query's list with a single global atomic, and the
+     * lanes write their keys behind that base. Three barriers, all
+     * unconditional. As is dead after the k loop's last barrier. */
+    int *lcnt = (int *)&As[0][0]; /* [GT_BM]: row count, then row base */
+    if (threadIdx.x < GT_BM) lcnt[threadIdx.x] = 0;
+    __syncthreads();
+    float bn[4];
+    bool c_ok[4];
 #pragma unroll
     for (int fj = 0; fj < 4; fj++) {
       int64_t col = col0 + wc + fj * 16 + (lane & 15);
-      if (col >= n) continue;
+      c_ok[fj] = col < n;
+      bn[fj] = (fp.l2 && c_ok[fj]) ? fp.bnorms[fp.col_base + col] : 0.0f;
+    }
+    const uint32_t id0 = (uint32_t)(fp.col_base + col0 + wc + (lane & 15));
+    auto key_of = [&](float dot, float qn, int fj) {
+      float dist = fp.l2 ? fmaf(-2.0f, dot, qn + bn[fj]) : dot;
+      return gamma_make_key<IP>(dist, id0 + fj * 16);
+    };
+    /* per row: bits 0..3 = which of the lane's columns pass, bits 8.. =
+     * the lane's offset among the row's passing keys in this tile */
+    uint32_t pk[4][4];
+#pragma unroll
+    for (int fi = 0; fi < 4; fi++) {
 #pragma unroll
       for (int r = 0; r < 4; r++) {
-        int qi = row0 + wr + fi * 16 + (lane >> 4) * 4 + r;
-        if (qi < nq) out[(int64_t)qi * n + col] = acc[fi][fj][r];
+        const int row = wr + fi * 16 + (lane >> 4) * 4 + r;
+        const int qi = row0 + row;
+        uint32_t m = 0;
+        if (qi < nq) {
+          const uint64_t tau = fp.thresh[(int64_t)qi * fp.thresh_ld];
+          const float qn = fp.l2 ? fp.qnorms[qi] : 0.0f;
+#pragma unroll
+          for (int fj = 0; fj < 4; fj++)
+            if (c_ok[fj] && key_of(acc[fi][fj][r], qn, fj) < tau)
+              m |= 1u << fj;
+        }
+        if (m) m |= (uint32_t)atomicAdd(&lcnt[row], __popc(m)) << 8;
+        pk[fi][r] = m;
+      }
+    }
+    __syncthreads();
+    if (threadIdx.x < GT_BM) { /* a count > 0 is a row below nq */
+      const int c = lcnt[threadIdx.x];
+      if (c > 0)
+        lcnt[threadIdx.x] = atomicAdd(&fp.cand_cnt[row0 + threadIdx.x], c);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int fi = 0; fi < 4; fi++) {
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const uint32_t m = pk[fi][r];
+        if (!m) continue;
+        const int row = wr + fi * 16 + (lane >> 4) * 4 + r;
+        const int qi = row0 + row;
+        const float qn = fp.l2 ? fp.qnorms[qi] : 0.0f;
+        uint64_t *dst = fp.cand + (int64_t)qi * fp.cap;
+        int idx = lcnt[row] + (int)(m >> 8);
+#pragma unroll
+        for (int fj = 0; fj < 4; fj++) {
+          if (!((m >> fj) & 1u)) continue;
+          if (idx < fp.cap) dst[idx] = key_of(acc[fi][fj][r], qn, fj);
+          idx++;
+        }
       }
     }
   }
 }
 
+__global__ void __launch_bounds__(WG)
+k_dots_mfma_tiled(const float *__restrict__ Q, int nq,
+                  const float *__restrict__ B, int64_t n, int d,
+                  float *__restrict__ out) {
+  gamma_dots_tile<false, false>(Q, nq, B, n, d, out, GammaDotsFilter{});
+}
+
+/* the same GEMM behind a device-side switch: returns at entry when
+ * *run_if == 0 (coarse assign's overflow fallback; normally all of its
+ * workgroups are empty) */
+__global__ void __launch_bounds__(WG)
+k_dots_mfma_tiled_if(const float *__restrict__ Q, int nq,
+                     const float *__restrict__ B, int64_t n, int d,
+                     float *__restrict__ out,
+                     const int *__restrict__ run_if) {
+  if (*run_if == 0) return; /* uniform: before any barrier */
+  gamma_dots_tile<false, false>(Q, nq, B, n, d, out, GammaDotsFilter{});
+}
+
+/* 4 waves/SIMD like the plain kernel (its LDS allows 4 workgroups per CU):
+ * without the bound the epilogue's hoisted threshold loads cost a wave */
+template <bool IP>
+__global__ void __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4)))
+k_dots_mfma_tiled_filter(const float *__restrict__ Q, int nq,
+                         const float *__restrict__ B, int64_t n, int d,
+                         GammaDotsFilter fp) {
+  gamma_dots_tile<true, IP>(Q, nq, B, n, d, nullptr, fp);
+}
+
 hipError_t gk::dots_mfma(hipStream_t s, const float *Q, int nq,
-                         const float *B, int64_t n, int d, float *out) {
+                         const float *B, int64_t n, int d, float *out,
+                         const int *run_if) {
   if (nq == 0 || n == 0) return hipSuccess;
   if (nq >= 64 && n >= 64) {
     dim3 grid((uint32_t)((n + GT_BM - 1) / GT_BM),
               (uint32_t)((nq + GT_BM - 1) / GT_BM));
-    k_dots_mfma_tiled<<<grid, dim3(WG), 0, s>>>(Q, nq, B, n, d, out);
+    if (run_if)
+      k_dots_mfma_tiled_if<<<grid, dim3(WG), 0, s>>>(Q, nq, B, n, d, out,
+                                                     run_if);
+    else
+      k_dots_mfma_tiled<<<grid, dim3(WG), 0, s>>>(Q, nq, B, n, d, out);
+  } else if (run_if) {
+    return hipErrorInvalidValue; /* only the tiled kernel has the switch */
   } else {
     dim3 grid((uint32_t)((n + 15) / 16), (uint32_t)((nq + 63) / 64));
     k_dots_mfma<<<grid, dim3(WG), 0, s>>>(Q, nq, B, n, d, out);
@@ -224,14 +358,13 @@ k_select_from_dots(int nq, int64_t ncols, int64_t col_base, int64_t ld,
  * pushes per wave ~ k2 * ln(ncols/k2)). Exact: same key order as the
  * block path (both validated against each other in tests). */
 template <bool IP>
-__global__ void __launch_bounds__(512)
-k_select_from_dots_wave(int nq, int64_t ncols, int64_t col_base,
-                        int64_t ld, const float *__restrict__ dots,
-                        const float *__restrict__ qnorms,
-                        const float *__restrict__ bnorms, int l2,
-                        const uint32_t *__restrict__ bitmap, int k2,
-                        uint64_t *__restrict__ state_keys, int seeded) {
-  extern __shared__ char smem[];
+__device__ __forceinline__ void
+gamma_select_wave(char *smem, int nq, int64_t ncols, int64_t col_base,
+                  int64_t ld, const float *__restrict__ dots,
+                  const float *__restrict__ qnorms,
+                  const float *__restrict__ bnorms, int l2,
+                  const uint32_t *__restrict__ bitmap, int k2,
+                  uint64_t *__restrict__ state_keys, int seeded) {
   const int nw = 512 / 64;
   uint64_t *wb = (uint64_t *)smem;
   int *cnts = (int *)(wb + (size_t)nw * GAMMA_WSEL_CAP);
@@ -297,12 +430,90 @@ k_select_from_dots_wave(int nq, int64_t ncols, int64_t col_base,
     state_keys[(int64_t)q * k2 + i] = sel.buf[i];
 }
 
+template <bool IP>
+__global__ void __launch_bounds__(512)
+k_select_from_dots_wave(int nq, int64_t ncols, int64_t col_base,
+                        int64_t ld, const float *__restrict__ dots,
+                        const float *__restrict__ qnorms,
+                        const float *__restrict__ bnorms, int l2,
+                        const uint32_t *__restrict__ bitmap, int k2,
+                        uint64_t *__restrict__ state_keys, int seeded) {
+  extern __shared__ char smem[];
+  gamma_select_wave<IP>(smem, nq, ncols, col_base, ld, dots, qnorms, bnorms,
+                        l2, bitmap, k2, state_keys, seeded);
+}
+
+/* the same select behind a device-side switch (see k_dots_mfma_tiled_if) */
+template <bool IP>
+__global__ void __launch_bounds__(512)
+k_select_from_dots_wave_if(int nq, int64_t ncols, int64_t col_base,
+                           int64_t ld, const float *__restrict__ dots,
+                           const float *__restrict__ qnorms,
+                           const float *__restrict__ bnorms, int l2,
+                           const uint32_t *__restrict__ bitmap, int k2,
+                           uint64_t *__restrict__ state_keys, int seeded,
+                           const int *__restrict__ run_if) {
+  extern __shared__ char smem[];
+  if (*run_if == 0) return;
+  gamma_select_wave<IP>(smem, nq, ncols, col_base, ld, dots, qnorms, bnorms,
+                        l2, bitmap, k2, state_keys, seeded);
+}
+
+/* Coarse assign, final select (gk::coarse_select phase 3): wave per query
+ * like k_select_from_dots_wave. state_keys[q] holds the sorted top-k2 of
+ * the seed columns; the candidates of the filtered GEMM (all below the
+ * k2-th seed) are merged in and the sorted top-k2 written back. Keys are
+ * compared as they are, so the metric does not matter here. A query whose
+ * counter ran past cap lost candidates: it raises *overflow, and the
+ * caller's switched full-width pass then rewrites the whole group. */
+__global__ void __launch_bounds__(512)
+k_coarse_final_select(int nq, int k2, int cap,
+                      const uint64_t *__restrict__ cand,
+                      const int *__restrict__ cand_cnt,
+                      uint64_t *__restrict__ state_keys,
+                      int *__restrict__ overflow) {
+  extern __shared__ char smem[];
+  const int nw = 512 / 64;
+  uint64_t *wb = (uint64_t *)smem;
+  int *cnts = (int *)(wb + (size_t)nw * GAMMA_WSEL_CAP);
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int q = blockIdx.x * nw + wave;
+  if (q >= nq) return; /* q is wave-uniform: the whole wave exits */
+  int m = cand_cnt[q];
+  if (m > cap) {
+    if (lane == 0) *overflow = 1;
+    m = cap;
+  }
+  if (m == 0) return; /* the seeds stand as they are */
+
+  GammaWaveSelector sel;
+  sel.init(wb + (size_t)wave * GAMMA_WSEL_CAP, cnts + wave, k2);
+  for (int i = lane; i < k2; i += 64) {
+    uint64_t kk = state_keys[(int64_t)q * k2 + i];
+    if (kk != GAMMA_KEY_EMPTY) {
+      int idx = atomicAdd(sel.cnt, 1);
+      sel.buf[sel.k + idx] = kk;
+    }
+  }
+  sel.finish();
+  const uint64_t *row = cand + (int64_t)q * cap;
+  for (int c0 = 0; c0 < m; c0 += 64) {
+    int c = c0 + lane;
+    if (c < m) sel.push(row[c]);
+    sel.maybe_flush(64);
+  }
+  sel.finish();
+  for (int i = lane; i < k2; i += 64)
+    state_keys[(int64_t)q * k2 + i] = sel.buf[i];
+}
+
 hipError_t gk::select_from_dots(hipStream_t s, int nq, int64_t ncols,
                                 int64_t col_base, int64_t ld,
                                 const float *dots, const float *qnorms,
                                 const float *bnorms, bool l2, bool ip_order,
                                 const uint32_t *bitmap, int k2,
-                                uint64_t *state_keys, bool seeded) {
+                                uint64_t *state_keys, bool seeded,
+                                const int *run_if) {
   /* k2 <= 192: seeds (k2 keys) plus one 64-push interval must fit the
    * wave cap (GAMMA_WSEL_CAP - k2), with slack; covers every coarse
    * assign (nprobe). Larger k2 (FLAT top-k accumulation) -> block path. */
@@ -310,6 +521,17 @@ hipError_t gk::select_from_dots(hipStream_t s, int nq, int64_t ncols,
     const int nw = 512 / 64;
     size_t smem = (size_t)nw * GAMMA_WSEL_CAP * 8 + nw * sizeof(int);
     dim3 g((uint32_t)((nq + nw - 1) / nw));
+    if (run_if) {
+      if (ip_order)
+        k_select_from_dots_wave_if<true><<<g, dim3(512), smem, s>>>(
+            nq, ncols, col_base, ld, dots, qnorms, bnorms, l2 ? 1 : 0,
+            bitmap, k2, state_keys, seeded ? 1 : 0, run_if);
+      else
+        k_select_from_dots_wave_if<false><<<g, dim3(512), smem, s>>>(
+            nq, ncols, col_base, ld, dots, qnorms, bnorms, l2 ? 1 : 0,
+            bitmap, k2, state_keys, seeded ? 1 : 0, run_if);
+      return hipGetLastError();
+    }
     if (ip_order)
       k_select_from_dots_wave<true><<<g, dim3(512), smem, s>>>(
           nq, ncols, col_base, ld, dots, qnorms, bnorms, l2 ? 1 : 0,
@@ -320,6 +542,7 @@ hipError_t gk::select_from_dots(hipStream_t s, int nq, int64_t ncols,
           bitmap, k2, state_keys, seeded ? 1 : 0);
     return hipGetLastError();
   }
+  if (run_if) return hipErrorInvalidValue; /* wave kernel only */
   size_t smem = (GAMMA_SORT_CAP + k2) * 8 + 4 * sizeof(int);
   if (ip_order)
     k_select_from_dots<true><<<dim3(nq), dim3(WG), smem, s>>>(
@@ -330,6 +553,110 @@ hipError_t gk::select_from_dots(hipStream_t s, int nq, int64_t ncols,
         nq, ncols, col_base, ld, dots, qnorms, bnorms, l2 ? 1 : 0, bitmap,
         k2, state_keys, seeded ? 1 : 0);
   return hipGetLastError();
+}
+
+/* ------------------------------------- coarse assign, seed-filtered GEMM */
+/* GAMMA_FUSE_COARSE=0 keeps coarse assign on the full dots matrix (A/B
+ * runs of one build, and tests that compare the two paths) */
+static bool gamma_fuse_coarse() {
+  const char *e = getenv("GAMMA_FUSE_COARSE");
+  return !(e && e[0] == '0' && e[1] == 0);
+}
+
+/* experiment knobs: seed columns (a multiple of 128) and candidate slots
+ * per query */
+int gk::coarse_seed_cols() {
+  const char *e = getenv("GAMMA_COARSE_SEED_COLS");
+  if (e && atoi(e) > 0 && atoi(e) % GT_BM == 0) return atoi(e);
+  return 4096; /* headline sweep: profiles/README.md "Coarse filter" */
+}
+int gk::coarse_cand_cap() {
+  const char *e = getenv("GAMMA_COARSE_CAND_CAP");
+  if (e && atoi(e) > 0) return atoi(e);
+  return 1024;
+}
+
+bool gk::coarse_can_filter(int nq, int64_t nlist, int d, int nprobe,
+                           int n1) {
+  if (!gamma_fuse_coarse()) return false;
+  if (n1 <= 0) n1 = gk::coarse_seed_cols();
+  if (n1 % GT_BM != 0 || nprobe < 1 || nprobe > 192) return false;
+  /* exactness needs no relation of n1 to nprobe; n1 >= nprobe makes the
+   * threshold a real key. The default 4096 is > 4 * 192; the expected
+   * candidates per query are about nprobe * (nlist / n1 - 1). */
+  if (n1 < nprobe || nq < 64 || d <= 0 || (d & 3)) return false;
+  return nlist >= 2 * (int64_t)n1;
+}
+
+hipError_t gk::coarse_select(hipStream_t s, const float *Q, int nq,
+                             const float *B, int64_t nlist, int d,
+                             const float *qnorms, const float *bnorms,
+                             bool l2, bool ip_order, int nprobe, int n1,
+                             int cap, float *dots, uint64_t *cand,
+                             int *cand_cnt, uint64_t *sel_keys) {
+  if (nq == 0 || nlist == 0) return hipSuccess;
+  if (n1 <= 0) n1 = gk::coarse_seed_cols();
+  if (cap <= 0) cap = gk::coarse_cand_cap();
+  hipError_t e;
+  if (!gk::coarse_can_filter(nq, nlist, d, nprobe, n1)) {
+    e = gk::dots_mfma(s, Q, nq, B, nlist, d, dots);
+    if (e != hipSuccess) return e;
+    return gk::select_from_dots(s, nq, nlist, 0, nlist, dots, qnorms, bnorms,
+                                l2, ip_order, nullptr, nprobe, sel_keys,
+                                false);
+  }
+  int *overflow = cand_cnt + nq;
+  e = hipMemsetAsync(cand_cnt, 0, ((size_t)nq + 1) * sizeof(int), s);
+  if (e != hipSuccess) return e;
+  /* 1. seeds: the exact sorted top-nprobe of the first n1 columns; its
+   * last key bounds the full row's nprobe-th key from above */
+  e = gk::dots_mfma(s, Q, nq, B, n1, d, dots);
+  if (e != hipSuccess) return e;
+  e = gk::select_from_dots(s, nq, n1, 0, n1, dots, qnorms, bnorms, l2,
+                           ip_order, nullptr, nprobe, sel_keys, false);
+  if (e != hipSuccess) return e;
+  /* 2. the other columns: keep the keys below that bound */
+  {
+    const int64_t n = nlist - n1;
+    GammaDotsFilter fp;
+    fp.qnorms = qnorms;
+    fp.bnorms = bnorms;
+    fp.thresh = sel_keys + (nprobe - 1);
+    fp.thresh_ld = nprobe;
+    fp.col_base = n1;
+    fp.l2 = l2 ? 1 : 0;
+    fp.cand = cand;
+    fp.cand_cnt = cand_cnt;
+    fp.cap = cap;
+    dim3 grid((uint32_t)((n + GT_BM - 1) / GT_BM),
+              (uint32_t)((nq + GT_BM - 1) / GT_BM));
+    const float *Bt = B + (size_t)n1 * d;
+    if (ip_order)
+      k_dots_mfma_tiled_filter<true><<<grid, dim3(WG), 0, s>>>(Q, nq, Bt, n,
+                                                               d, fp);
+    else
+      k_dots_mfma_tiled_filter<false><<<grid, dim3(WG), 0, s>>>(Q, nq, Bt, n,
+                                                                d, fp);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  /* 3. seeds + candidates -> sorted top-nprobe */
+  {
+    const int nw = 512 / 64;
+    size_t smem = (size_t)nw * GAMMA_WSEL_CAP * 8 + nw * sizeof(int);
+    k_coarse_final_select<<<dim3((uint32_t)((nq + nw - 1) / nw)), dim3(512),
+                            smem, s>>>(nq, nprobe, cap, cand, cand_cnt,
+                                       sel_keys, overflow);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  /* a candidate list that overflowed: the full-width pair rewrites the
+   * group's keys; with the flag clear both launches are empty workgroups */
+  e = gk::dots_mfma(s, Q, nq, B, nlist, d, dots, overflow);
+  if (e != hipSuccess) return e;
+  return gk::select_from_dots(s, nq, nlist, 0, nlist, dots, qnorms, bnorms,
+                              l2, ip_order, nullptr, nprobe, sel_keys, false,
+                              overflow);
 }
 
 /* ----------------------------------------------- full-sort row select */

@@ -273,4 +273,24 @@ int GammaKTestRabitqSvalBuckets(int nlist, int d, const void *bks_dev,
                                          centroids));
 }
 
+int GammaKTestCoarseSelect(const float *Q, int nq, const float *B,
+                           int64_t nlist, int d, const float *qnorms,
+                           const float *bnorms, int l2, int ip_order,
+                           int nprobe, int n1, int cap, float *dots,
+                           uint64_t *cand, int *cand_cnt,
+                           uint64_t *sel_keys) {
+  return kt_done(gk::coarse_select(nullptr, Q, nq, B, nlist, d, qnorms,
+                                   bnorms, l2 != 0, ip_order != 0, nprobe, n1,
+                                   cap, dots, cand, cand_cnt, sel_keys));
+}
+
+int GammaKTestCoarseCanFilter(int nq, int64_t nlist, int d, int nprobe,
+                              int n1, int *knobs2) {
+  if (knobs2) {
+    knobs2[0] = gk::coarse_seed_cols();
+    knobs2[1] = gk::coarse_cand_cap();
+  }
+  return gk::coarse_can_filter(nq, nlist, d, nprobe, n1) ? 1 : 0;
+}
+
 } /* extern "C" */

@@ -79,6 +79,11 @@ def _lib():
         L.GammaKTestRowNorms.argtypes = [vp, i64, i32, vp]
         L.GammaKTestExtractProbe0.argtypes = [i32, i32, vp, vp]
         L.GammaKTestRabitqSvalBuckets.argtypes = [i32, i32, vp, vp]
+        L.GammaKTestCoarseSelect.argtypes = [
+            vp, i32, vp, i64, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp,
+            vp, vp]
+        L.GammaKTestCoarseCanFilter.argtypes = [
+            i32, i64, i32, i32, i32, c.POINTER(c.c_int)]
         _ready = True
     return L
 
@@ -229,6 +234,50 @@ def sort_rows(keys, k, ip):
     _call("GammaKTestSortRows", nq, ncand, k, _p(keys, torch.int64),
           int(bool(ip)), _p(od), _p(oi))
     return od, oi
+
+
+def coarse_can_filter(nq, nlist, d, nprobe, n1=0):
+    """gk::coarse_can_filter under the current GAMMA_FUSE_COARSE (n1 = 0:
+    the GAMMA_COARSE_SEED_COLS knob)."""
+    return _lib().GammaKTestCoarseCanFilter(nq, nlist, d, nprobe, n1,
+                                            None) == 1
+
+
+def coarse_knobs():
+    """(seed columns, candidate cap) as the library reads its knobs"""
+    out = (ctypes.c_int * 2)()
+    _lib().GammaKTestCoarseCanFilter(64, 1 << 20, 4, 1, 0, out)
+    return out[0], out[1]
+
+
+def coarse_select(Q, B, nprobe, l2, ip_order, n1, cap, qnorms=None,
+                  bnorms=None):
+    """gk::coarse_select: the seed-filtered coarse assign of Q (nq, d) over
+    the centroids B (nlist, d). Returns (keys (nq, nprobe) int64 bits,
+    cand_cnt (nq,) int32, overflow flag). The counters are pre-filled with
+    -7: they keep that value where the predicate sent the call down the
+    plain full-width path."""
+    assert Q.is_contiguous() and B.is_contiguous()
+    nq, d = Q.shape
+    nlist = B.shape[0]
+    assert B.shape[1] == d and d % 4 == 0 and cap >= 1
+    if l2:
+        assert qnorms is not None and bnorms is not None
+        assert qnorms.numel() >= nq and bnorms.numel() >= nlist
+    dev = Q.device
+    dots = torch.full((nq, nlist), float("nan"), dtype=torch.float32,
+                      device=dev)
+    cand = torch.full((nq, cap), 0x5A5A5A5A5A5A5A5A, dtype=torch.int64,
+                      device=dev)
+    cnt = torch.full((nq + 1,), -7, dtype=torch.int32, device=dev)
+    keys = torch.full((nq, nprobe), 0x5A5A5A5A5A5A5A5A, dtype=torch.int64,
+                      device=dev)
+    _call("GammaKTestCoarseSelect", _p(Q, torch.float32), nq,
+          _p(B, torch.float32), nlist, d, _p(qnorms, torch.float32),
+          _p(bnorms, torch.float32), int(bool(l2)), int(bool(ip_order)),
+          nprobe, n1, cap, _p(dots), _p(cand), _p(cnt), _p(keys))
+    cnt = cnt.cpu().numpy()
+    return keys, cnt[:nq], int(cnt[nq])
 
 
 def unpack_keys(keys, ip):
