@@ -354,6 +354,21 @@ def test_scan8_generic_dword_aligned_lists(d, M, ip):
 
 
 @pytest.mark.parametrize("ip", [False, True], ids=["l2", "ip"])
+@pytest.mark.parametrize("d,M", [(48, 12)])
+def test_scan8_generic_kill_flag(d, M, ip):
+    """The list-by-list walk the 4-bit generic path shares, from its 8-bit
+    side: a flag raised before the launch leaves every row EMPTY, ids -1;
+    a flag left at 0 changes nothing."""
+    c = _case(d, M, 256, ip)
+    for name, S, k2 in (("rows8", 1, 10), ("pairs", 2, 1024)):
+        keys, _, ids = c.run(name, S, k2, kill_flag=1)
+        assert keys.shape == (8, S, k2)
+        assert (keys == kr._EMPTY).all(), (name, S, k2)
+        assert (ids == -1).all()
+        _check(c, name, S, k2, kill_flag=0)
+
+
+@pytest.mark.parametrize("ip", [False, True], ids=["l2", "ip"])
 @pytest.mark.parametrize("d,M", FAST8)
 def test_scan8_fast_m64_m96_bitmap_and_qmap(d, M, ip):
     c = _case(d, M, 256, ip)

@@ -1,7 +1,8 @@
 /*
  * binary_kernels.hpp — Hamming-distance kernels of the BINARYIVF index
  * (gamma_index_binary_ivf.cc). Included at the end of kernels.hip: it
- * uses that file's WG and GAMMA_SCAN_BS launch knob, and scan_walk.hpp.
+ * uses that file's WG, the GAMMA_SCAN_BS launch knob (gamma_scan_bs in
+ * ivfpq_scan_kernels.hpp) and scan_walk.hpp.
  *
  * A binary vector of d bits is W = d/32 little-endian u32 words (bit i of
  * the vector is bit i&31 of word i>>5, i.e. LSB-first inside each byte).

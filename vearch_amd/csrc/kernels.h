@@ -199,64 +199,81 @@ hipError_t pq_sterm(hipStream_t s, int64_t n, int M, int ksub, int nlist,
 hipError_t pq_sterm_buckets(hipStream_t s, int nlist, int M, int ksub,
                             const GammaBucketDev *bks, const float *btab);
 
-/* IVFPQ fused search: one workgroup per query; stages the query-level
- * table ONCE (L2: A_q from atab, dis = coarse_dis + S_v + sum A[c_m];
- * IP: the h:164-167 query table, dis = dis0 + sum T[c_m]), then scans
- * the probed lists (h:923-953 semantics). out_keys: nq x k2. */
-/* S = probe-split factor: S sub-workgroups per query (out_keys is
- * nq x S x k2; merge with sort_rows). S>1 serves small batches. */
-/* qmap: optional query schedule — workgroup b serves query
- * qmap[b/S]. The engine sorts large batches by their first probed
- * list so neighbouring workgroups scan the same lists while they are
- * L2/LLC-resident (the 10M-doc code store is ~400 MB against the
- * 256 MiB Infinity Cache — unordered queries re-fetch every list
- * ~nq*nprobe/nlist times from DRAM). Results are identical: the
- * selector's top-k2 is order-independent and outputs are written at
- * the ORIGINAL query row. */
-/* ksub=16 runs k_ivfpq_scan4 on packed 4-bit entries (M/2 bytes, low
- * nibble = even sub-quantizer) with an M x 16 table; same contract. */
-/* L2 table source: when ivfpq_scan_builds_table(M, ksub, k2) the kernel
- * (8-bit codes, M in {16,32,64,96}, k2 + block size within the selector
- * cap) builds the query table itself from codebooks + cwn (pq_cwn) and
- * atab may be null (unless the launch is wide, below); otherwise atab
- * (pq_tables_a) is required and cwn may be null. Inner product needs
- * neither. Both functions read the same launch knobs: GAMMA_SCAN_BS (256|512 threads; default 512) and
- * GAMMA_ADC_C (1|2 codes staged per thread, 4-bit kernel only — the
- * 8-bit fast path accepts and ignores it). Results do not depend on
- * either knob. */
-/* Wide tables: where k_ivfpq_scan's resident table (M KB of LDS) cannot
- * launch — ivfpq_scan_is_wide(d, M, ksub, k2); M >= 144 always, M of 136
- * to 140 depending on k2 and d — 8-bit codes run k_ivfpq_scan_wide, which
- * keeps IVFPQ_WIDE_MS sub-quantizers of the table in LDS at a time and
- * walks tiles of ivfpq_wide_tile() entries. It reads the query table from
- * `atab` for BOTH metrics: pq_tables_a for L2, pq_tables_ip for inner
- * product (nq x M x 256 floats; the caller bounds nq per launch).
- * GAMMA_SCAN_WIDE=1, read per launch, forces it at any M. Keys do not
- * depend on which kernel ran. */
+/* IVFPQ fused search (the kernels are in ivfpq_scan_kernels.hpp).
+ *
+ * 1. What the launch computes. One workgroup per (query, probe-split
+ *    part) stages the query-level table ONCE (L2: A_q, dis = coarse_dis +
+ *    S_v + sum A[c_m]; IP: the h:164-167 query table, dis = dis0 + sum
+ *    T[c_m]), then scans the probed lists (h:923-953 semantics) and keeps
+ *    the k2 best keys.
+ *    - S = probe-split factor: S sub-workgroups per query, out_keys is
+ *      nq x S x k2; merge with sort_rows. S = 1 gives nq x k2. S > 1 serves
+ *      small batches.
+ *    - qmap: optional query schedule — workgroup b serves query qmap[b/S].
+ *      The engine sorts large batches by their first probed list so
+ *      neighbouring workgroups scan the same lists while they are
+ *      L2/LLC-resident (the 10M-doc code store is ~400 MB against the
+ *      256 MiB Infinity Cache — unordered queries re-fetch every list
+ *      ~nq*nprobe/nlist times from DRAM). Results are identical: the
+ *      selector's top-k2 is order-independent and outputs are written at
+ *      the ORIGINAL query row.
+ *    - Keys do not depend on which kernel ran, nor on any knob below.
+ *
+ * 2. Which inputs a launch needs, by (ksub, metric, shape). The three
+ *    predicates below are the authority; ivfpq_scan_reads_table says what
+ *    the caller has to build.
+ *    - ksub = 16 runs k_ivfpq_scan4 on packed 4-bit entries (M/2 bytes, low
+ *      nibble = even sub-quantizer) with an M x 16 table; same contract.
+ *      L2 needs atab (pq_tables_a); inner product needs neither atab nor
+ *      cwn. ivfpq_scan_fits bounds M and d.
+ *    - ksub = 256, wide — ivfpq_scan_is_wide(d, M, ksub, k2): where
+ *      k_ivfpq_scan's resident table (M KB of LDS) cannot launch (M >= 144
+ *      always, M of 136 to 140 depending on k2 and d; a fast-path M is wide
+ *      too once 4*d fills the LDS), 8-bit codes run k_ivfpq_scan_wide, which
+ *      keeps IVFPQ_WIDE_MS sub-quantizers of the table in LDS at a time and
+ *      walks tiles of ivfpq_wide_tile() entries. It reads the query table
+ *      from `atab` for BOTH metrics: pq_tables_a for L2, pq_tables_ip for
+ *      inner product (nq x M x 256 floats; the caller bounds nq per
+ *      launch). M % 4 == 0.
+ *    - ksub = 256, not wide, ivfpq_scan_builds_table(M, ksub, k2) (M in
+ *      {16,32,64,96}, k2 + block size within the selector cap): the kernel
+ *      builds the query table itself from codebooks + cwn (pq_cwn); atab
+ *      may be null. Inner product needs neither.
+ *    - ksub = 256, every other launch: L2 requires atab (pq_tables_a) and
+ *      cwn may be null. Inner product needs neither.
+ *    ivfpq_scan_fits(d, M, ksub): whether a table of this shape can be
+ *    scanned at every legal k2, for both metrics (the LDS bound on d, and
+ *    on M for 4-bit codes).
+ *
+ * 3. Knobs, read from the environment per launch by the launcher and the
+ *    predicates alike:
+ *    - GAMMA_SCAN_BS (256|512 threads; default 512).
+ *    - GAMMA_ADC_C (1|2 codes staged per thread, 4-bit kernel only — the
+ *      8-bit fast path accepts and ignores it).
+ *    - GAMMA_SCAN_WIDE=1 forces the wide kernel at any M.
+ *    - GAMMA_FUSE_RERANK=0 turns ivfpq_scan_can_fuse_rerank off.
+ *
+ * 4. Fused re-rank: with `rr` set the resident-table 8-bit kernel ends in
+ *    the epilogue of rerank_epilogue.hpp — exact distances of the query's
+ *    top-k2 in gk::rerank's own fmaf chain, one sort, top-k written to
+ *    rr->out_* — and out_keys is not touched (it may be null). Results are
+ *    bit-identical to ivfpq_scan + rerank + sort_rows. Legal where
+ *    ivfpq_scan_can_fuse_rerank: S == 1, 8-bit codes, not a wide launch,
+ *    d % 4 == 0. Any other launch with rr set, or rr->k outside [1, 2048],
+ *    is hipErrorInvalidValue and launches nothing. */
 enum { IVFPQ_WIDE_MS = 32, IVFPQ_WIDE_E = 4 };
 int ivfpq_wide_tile(); /* entries per tile at the current GAMMA_SCAN_BS */
 bool ivfpq_scan_is_wide(int d, int M, int ksub, int k2);
-/* whether a table of this shape can be scanned at every legal k2, for
- * both metrics (the LDS bound on d, and on M for 4-bit codes) */
 enum { IVFPQ_MAX_DIM = 16384, IVFPQ4_MAX_LDS_TERM = 131072 };
 bool ivfpq_scan_fits(int d, int M, int ksub);
+/* the wide kernel's inner-product table: out[q][m][j] = q_m . cw_mj */
 hipError_t pq_tables_ip(hipStream_t s, int nq, int d, int M,
                         const float *queries, const float *codebooks,
                         float *out);
 bool ivfpq_scan_builds_table(int M, int ksub, int k2);
-/* whether this launch reads `atab`, i.e. what the caller has to build:
- * every wide launch (both metrics, any M — a fast-path M is wide too once
- * 4*d fills the LDS), and L2 launches whose kernel builds no table */
+/* whether this launch reads `atab`: every wide launch (both metrics, any
+ * M), and L2 launches whose kernel builds no table */
 bool ivfpq_scan_reads_table(int d, int M, int ksub, int k2, bool ip);
-/* Fused re-rank: with `rr` set the resident-table 8-bit kernel ends in the
- * epilogue of rerank_epilogue.hpp — exact distances of the query's top-k2
- * in gk::rerank's own fmaf chain, one sort, top-k written to rr->out_* —
- * and out_keys is not touched (it may be null). Results are bit-identical
- * to ivfpq_scan + rerank + sort_rows. Legal where
- * ivfpq_scan_can_fuse_rerank: S == 1, 8-bit codes, not a wide launch,
- * d % 4 == 0. GAMMA_FUSE_RERANK=0, read per call, turns the predicate
- * off. Any other launch with rr set, or rr->k outside [1, 2048], is
- * hipErrorInvalidValue and launches nothing. */
 bool ivfpq_scan_can_fuse_rerank(int d, int M, int ksub, int k2, int S);
 hipError_t ivfpq_scan(hipStream_t s, int nq, int S, int d, int M, int ksub,
                       int nprobe,

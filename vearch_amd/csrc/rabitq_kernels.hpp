@@ -2,7 +2,8 @@
  * rabitq_kernels.hpp — kernels of the IVFRABITQ index (1-bit RaBitQ codes,
  * gamma_index_ivfrabitq.cc with nb_bits = 1). Included at the end of
  * kernels.hip after binary_kernels.hpp: it uses that file's gamma_bin_load,
- * kernels.hip's WG and GAMMA_SCAN_BS launch knob, and scan_walk.hpp.
+ * kernels.hip's WG, the GAMMA_SCAN_BS launch knob (gamma_scan_bs in
+ * ivfpq_scan_kernels.hpp) and scan_walk.hpp.
  *
  * An entry of a d-dimensional table is EW = d/32 + 2 little-endian words:
  * W = d/32 sign words (bit j of the vector is bit j&31 of word j>>5, the

@@ -2,7 +2,8 @@
  * scan_walk.hpp — the chunked probe walk shared by the fused IVF scan
  * kernels (k_ivfpq_scan's fast path, k_ivfpq_scan_wide, k_binivf_scan,
  * k_rabitq_scan). Included by kernels.hip behind select.hpp and kernels.h,
- * in front of binary_kernels.hpp and rabitq_kernels.hpp.
+ * in front of ivfpq_scan_kernels.hpp, binary_kernels.hpp and
+ * rabitq_kernels.hpp.
  *
  * A workgroup walks its probe subsequence in chunks of at most
  * GAMMA_SCAN_PCH lists. Per chunk: one thread per probe stores the list's
