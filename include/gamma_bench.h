@@ -291,6 +291,24 @@ int GammaKTestRabitqScan(int nq, int S, int d, int nprobe, int k2,
                          int ip, uint64_t *out_keys, const int *kill_flag);
 int GammaKTestRabitqSvalBuckets(int nlist, int d, const void *bks_dev,
                                 const float *centroids);
+/* The same three for nb_bits = 4 or 8. An entry is d * nb_bits / 8 + 8
+ * bytes: the unsigned codes u_j (nb_bits 4: nibble j & 7 of little-endian
+ * 32-bit word j >> 3; nb_bits 8: byte j), then A and Mul as little-endian
+ * fp32; svals hold sum_j u_j * c_j. GammaDebugGetList serves the lists of
+ * such a table in this form. */
+int GammaKTestRabitqEncodeEx(int nb_bits, int64_t n, int d, const float *x,
+                             const int32_t *asg, int asg_const, int nlist,
+                             const float *centroids, int ip,
+                             uint8_t *entries, float *svals);
+int GammaKTestRabitqScanEx(int nb_bits, int nq, int S, int d, int nprobe,
+                           int k2, const float *queries,
+                           const float *centroids, const void *buckets_dev,
+                           int nlist, const int64_t *probes,
+                           const uint32_t *bitmap, int ip,
+                           uint64_t *out_keys, const int *kill_flag);
+int GammaKTestRabitqSvalBucketsEx(int nb_bits, int nlist, int d,
+                                  const void *bks_dev,
+                                  const float *centroids);
 /* gk::coarse_select, the seed-filtered coarse assign (kernels.h): dots is
  * nq x nlist floats of scratch, cand nq x cap keys, cand_cnt nq + 1 ints
  * (per-query candidate counters, then the overflow flag), sel_keys the

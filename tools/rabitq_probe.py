@@ -7,6 +7,8 @@ the same nlist and nprobe, plus a FLAT table for the exact ground truth:
 
   * IVFRABITQ, nb_bits = 1: the scan reads 4 B id + 24 B entry (16 B sign
     bits, A, Mul) + 4 B sval = 32 B per entry, one LDS lookup per nibble;
+    --nb-bits 1,4,8 adds a table per further width (d * nb_bits / 8 + 8 B
+    entries, the table-free scan) to the same run;
   * IVFPQ m = 32, 8-bit codes: 4 B id + 32 B code + 4 B S term = 40 B per
     entry, one LDS lookup per code byte.
 
@@ -77,8 +79,14 @@ def main():
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--steps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--nb-bits", default="1",
+                    help="comma-separated IVFRABITQ code widths (1, 4, 8): "
+                         "one table each, all timed in the same run")
     ap.add_argument("--out", default="profiles/rabitq_probe.json")
     args = ap.parse_args()
+    widths = [int(b) for b in args.nb_bits.split(",")]
+    if not widths or any(b not in (1, 4, 8) for b in widths):
+        ap.error("--nb-bits takes 1, 4 and 8")
     if args.steps < 5:
         ap.error("--steps must be >= 5 (medians)")
     n, d = args.db_size, args.d
@@ -99,9 +107,9 @@ def main():
     common = ('"ncentroids": %d, "metric_type": "L2", '
               '"training_threshold": %d, "bucket_max_size": 12800000'
               % (args.nlist, train_n))
-    specs = [
-        ("IVFRABITQ nb_bits=1 L2", "IVFRABITQ", '{%s, "nb_bits": 1}' % common,
-         d // 8 + 8),
+    specs = [("IVFRABITQ nb_bits=%d L2" % b, "IVFRABITQ",
+              '{%s, "nb_bits": %d}' % (common, b), d * b // 8 + 8)
+             for b in widths] + [
         ("IVFPQ m=%d 8-bit L2" % args.m, "IVFPQ",
          '{%s, "nsubvector": %d, "nbits_per_idx": 8}' % (common, args.m),
          args.m),
@@ -109,7 +117,10 @@ def main():
     tables = []
     for name, itype, params, code_bytes in specs:
         t0 = time.time()
-        eng = build("/tmp/gamma_rbqprobe_" + itype, base, d, itype, params)
+        wide = itype == "IVFRABITQ" and code_bytes != d // 8 + 8
+        eng = build("/tmp/gamma_rbqprobe_" + itype
+                    + ("_%d" % code_bytes if wide else ""), base, d, itype,
+                    params)
         tables.append({"table": name, "d": d, "code_bytes": code_bytes,
                        "scan_bytes_per_entry": 4 + code_bytes + 4,
                        "build_s": round(time.time() - t0, 1), "_eng": eng})
@@ -162,7 +173,7 @@ def main():
             del t[key]
         print(json.dumps(t), flush=True)
 
-    rb, pq = tables
+    rb, pq = tables[0], tables[-1]
     ratios = {str(rn): round(a["scan_gbytes_per_s"] / b["scan_gbytes_per_s"],
                              4)
               for rn, a, b in zip(RECALL_NUMS, rb["runs"], pq["runs"])}
@@ -180,6 +191,13 @@ def main():
                            / b["scan_gentries_per_s"], 4)
             for rn, a, b in zip(RECALL_NUMS, rb["runs"], pq["runs"])},
     }
+    if len(widths) > 1:  # the wider codes against the first width given
+        doc["byte_rate_ratio_over_nb_bits_%d" % widths[0]] = {
+            t["table"]: {str(rn): round(a["scan_gbytes_per_s"]
+                                        / b["scan_gbytes_per_s"], 4)
+                         for rn, a, b in zip(RECALL_NUMS, t["runs"],
+                                             rb["runs"])}
+            for t in tables[1:-1]}
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(doc, f, indent=1)

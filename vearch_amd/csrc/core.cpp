@@ -369,7 +369,8 @@ int IVFIndex::init(int d, const IndexParams &p, std::string *err) {
     if (d < 32 || d > kRabitqMaxDim || d % 32 != 0) return -1;
     M_ = 0;
     dsub_ = 0;
-    code_size_ = d / 8 + 8; /* sign bits, A, Mul */
+    if (p.nb_bits != 1 && p.nb_bits != 4 && p.nb_bits != 8) return -1;
+    code_size_ = d * p.nb_bits / 8 + 8; /* codes, A, Mul */
   } else {
     M_ = 0;
     dsub_ = 0;
@@ -913,6 +914,19 @@ int IVFIndex::pq_subspace_kmeans_(const float *sub_host, int64_t n,
   return 0;
 }
 
+/* IVFRABITQ: entries and svals of n vectors, by the table's code width */
+hipError_t IVFIndex::rabitq_encode_(hipStream_t s, int64_t n, const float *x,
+                                    const int32_t *asg, uint8_t *entries,
+                                    float *svals) {
+  if (params_.nb_bits == 1)
+    return gk::rabitq_encode(s, n, d_, x, asg, 0, nlist_,
+                             centroids_.as<float>(), params_.metric_ip,
+                             entries, svals);
+  return gk::rabitq_encode_ex(s, params_.nb_bits, n, d_, x, asg, 0, nlist_,
+                              centroids_.as<float>(), params_.metric_ip,
+                              entries, svals);
+}
+
 /* residuals -> bucket-format entries (code_size_ bytes each) */
 int IVFIndex::encode_entries_(hipStream_t s, int64_t n, const float *resid,
                               uint8_t *codes) {
@@ -1009,10 +1023,8 @@ int IVFIndex::add(const float *x_host, const int64_t *vids, int64_t n,
       /* sign bits + factors per vector, and its sval, in one launch */
       if (codes.reserve((size_t)cn * code_size_)) return -1;
       if (sterm.reserve((size_t)cn * 4)) return -1;
-      if (gk::rabitq_encode(s, cn, d_, xin, asg.as<int32_t>(), 0, nlist_,
-                            centroids_.as<float>(), params_.metric_ip,
-                            codes.as<uint8_t>(),
-                            sterm.as<float>()) != hipSuccess)
+      if (rabitq_encode_(s, cn, xin, asg.as<int32_t>(), codes.as<uint8_t>(),
+                         sterm.as<float>()) != hipSuccess)
         return -1;
       codes_h.resize((size_t)cn * code_size_);
       (void)hipMemcpy(codes_h.data(), codes.get(), (size_t)cn * code_size_,
@@ -1198,10 +1210,8 @@ int IVFIndex::prepare_fast_one(const float *vec_h, hipStream_t s,
   } else if (rabitq()) {
     if (codes.reserve((size_t)code_size_)) return -1;
     if (sterm.reserve(4)) return -1;
-    if (gk::rabitq_encode(s, 1, d_, xin, asg.as<int32_t>(), 0, nlist_,
-                          centroids_.as<float>(), params_.metric_ip,
-                          codes.as<uint8_t>(),
-                          sterm.as<float>()) != hipSuccess)
+    if (rabitq_encode_(s, 1, xin, asg.as<int32_t>(), codes.as<uint8_t>(),
+                       sterm.as<float>()) != hipSuccess)
       return -1;
     GAMMA_CHECK(hipStreamSynchronize(s));
     GAMMA_CHECK(hipMemcpy(code_out, codes.get(), (size_t)code_size_,
@@ -1595,11 +1605,18 @@ int IVFIndex::search(const float *q_dev, int nq, int k2, int nprobe,
     /* the factor A in the entries was encoded for the table's metric; a
      * request that overrides the metric is served as IVFPQ serves it, in
      * the requested key order over the codes as they are */
-    GAMMA_CHECK(gk::rabitq_scan(s, nq, S, d_, nprobe, k2, q_dev,
-                                centroids_.as<float>(),
-                                dev_buckets_.as<GammaBucketDev>(), nlist_,
-                                sc.probes.as<int64_t>(), bitmap_dev,
-                                metric_ip, out_keys_dev, kill_flag_dev));
+    if (params_.nb_bits == 1)
+      GAMMA_CHECK(gk::rabitq_scan(s, nq, S, d_, nprobe, k2, q_dev,
+                                  centroids_.as<float>(),
+                                  dev_buckets_.as<GammaBucketDev>(), nlist_,
+                                  sc.probes.as<int64_t>(), bitmap_dev,
+                                  metric_ip, out_keys_dev, kill_flag_dev));
+    else
+      GAMMA_CHECK(gk::rabitq_scan_ex(
+          s, params_.nb_bits, nq, S, d_, nprobe, k2, q_dev,
+          centroids_.as<float>(), dev_buckets_.as<GammaBucketDev>(), nlist_,
+          sc.probes.as<int64_t>(), bitmap_dev, metric_ip, out_keys_dev,
+          kill_flag_dev));
   } else if (binary()) {
     GAMMA_CHECK(gk::binivf_scan(s, nq, S, d_, nprobe, k2,
                                 (const uint32_t *)q_dev,
@@ -1682,7 +1699,7 @@ int IVFIndex::dump(FILE *f, hipStream_t s) const {
   if (rabitq()) {
     /* the factor A depends on the metric: record what the entries were
      * encoded for, so Load can refuse a table of the other metric */
-    int hdr[2] = {1 /* nb_bits */, params_.metric_ip ? 1 : 0};
+    int hdr[2] = {params_.nb_bits, params_.metric_ip ? 1 : 0};
     fwrite(hdr, 4, 2, f);
   }
   const size_t entry =
@@ -1743,12 +1760,13 @@ int IVFIndex::load(FILE *f, hipStream_t s, std::string *err) {
   if (rabitq()) {
     int hdr[2] = {0, 0};
     if (fread(hdr, 4, 2, f) != 2) return -1;
-    if (hdr[0] != 1 || (hdr[1] != 0) != params_.metric_ip) {
+    if (hdr[0] != params_.nb_bits || (hdr[1] != 0) != params_.metric_ip) {
       if (err)
         *err = std::string("dump IVFRABITQ codes (nb_bits ") +
                std::to_string(hdr[0]) + ", metric " +
                (hdr[1] ? "InnerProduct" : "L2") +
-               ") != table (nb_bits 1, metric " +
+               ") != table (nb_bits " + std::to_string(params_.nb_bits) +
+               ", metric " +
                (params_.metric_ip ? "InnerProduct" : "L2") + ")";
       return -1;
     }
@@ -1816,9 +1834,14 @@ int IVFIndex::load(FILE *f, hipStream_t s, std::string *err) {
       return -1;
     GAMMA_CHECK(hipStreamSynchronize(s));
   } else if (rabitq()) {
-    if (gk::rabitq_sval_buckets(s, nlist_, d_,
-                                dev_buckets_.as<GammaBucketDev>(),
-                                centroids_.as<float>()) != hipSuccess)
+    if ((params_.nb_bits == 1
+             ? gk::rabitq_sval_buckets(s, nlist_, d_,
+                                       dev_buckets_.as<GammaBucketDev>(),
+                                       centroids_.as<float>())
+             : gk::rabitq_sval_buckets_ex(s, params_.nb_bits, nlist_, d_,
+                                          dev_buckets_.as<GammaBucketDev>(),
+                                          centroids_.as<float>())) !=
+        hipSuccess)
       return -1;
     GAMMA_CHECK(hipStreamSynchronize(s));
   }

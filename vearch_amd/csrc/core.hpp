@@ -198,11 +198,12 @@ class Bitmap {
  * the same float-typed buffers the other kinds use (only copied, never
  * computed on). The vector width the Engine and IVFIndex carry for such a
  * table is therefore W; the bit count is kept next to it. */
-/* IVFRABITQ (gamma_index_ivfrabitq.cc, nb_bits = 1): float vectors like
- * IVFPQ — raw store, k-means, GEMM coarse assign and the exact re-rank leg
- * are shared — with list entries of d/8 + 8 code bytes (sign bits, then the
- * factors A and Mul) plus one device-only sval per entry, the shape of an
- * IVFPQ entry. See rabitq_kernels.hpp. */
+/* IVFRABITQ (gamma_index_ivfrabitq.cc, nb_bits = 1, 4 or 8): float vectors
+ * like IVFPQ — raw store, k-means, GEMM coarse assign and the exact re-rank
+ * leg are shared — with list entries of d * nb_bits / 8 + 8 code bytes (the
+ * codes, then the factors A and Mul) plus one device-only sval per entry,
+ * the shape of an IVFPQ entry. See rabitq_kernels.hpp (1 bit) and
+ * rabitq_ex_kernels.hpp (4 and 8 bits). */
 enum class IndexKind { FLAT, IVFPQ, IVFFLAT, BINARYIVF, IVFRABITQ };
 
 struct IndexParams {
@@ -378,6 +379,10 @@ class IVFIndex {
                           int seed_off);
   int encode_entries_(hipStream_t s, int64_t n, const float *resid,
                       uint8_t *codes);
+  /* IVFRABITQ: gk::rabitq_encode or, for nb_bits 4 / 8, rabitq_encode_ex */
+  hipError_t rabitq_encode_(hipStream_t s, int64_t n, const float *x,
+                            const int32_t *asg, uint8_t *entries,
+                            float *svals);
   int update_dev_buckets(hipStream_t s);
   bool bucket_compactable_(int b, float min_ratio) const;
   /* OPQ-NP training: alternate PQ fit and orthogonal Procrustes

@@ -95,20 +95,21 @@ int Engine::create_table(const std::string &name,
     params_.metric_ip = false;
     params_.has_opq = false;
   } else if (index_type_ == "IVFRABITQ") {
-    /* IVFRABITQModelParams (gamma_index_ivfrabitq.h:337-425). Only the
-     * 1-bit code is built; the reference's default nb_bits is 4, so an
-     * absent value is refused too rather than silently served by a
-     * different index. */
+    /* IVFRABITQModelParams (gamma_index_ivfrabitq.h:337-425). The code
+     * widths built are 1, 4 and 8 (whole fields per 32-bit word); the
+     * value must be given: an absent one stays refused rather than being
+     * read as the reference's default. */
     params_.kind = IndexKind::IVFRABITQ;
     params_.has_opq = false;
-    if (params_.nb_bits != 1) {
+    if (params_.nb_bits != 1 && params_.nb_bits != 4 &&
+        params_.nb_bits != 8) {
       if (err)
         *err = std::string("IVFRABITQ nb_bits ") +
                (params_.nb_bits == 0
                     ? "is absent (the reference default is 4)"
                     : "= " + std::to_string(std::max(params_.nb_bits, 0))) +
-               ": this engine supports nb_bits: 1 only, and it must be "
-               "given explicitly";
+               ": this engine supports nb_bits: 1, nb_bits: 4 and "
+               "nb_bits: 8, and the value must be given explicitly";
       return -1;
     }
     if (params_.qb < 0 || params_.qb > 8) {

@@ -399,4 +399,23 @@ hipError_t rabitq_scan(hipStream_t s, int nq, int S, int d, int nprobe,
                        const int64_t *probes, const uint32_t *bitmap, bool ip,
                        uint64_t *out_keys, const int *kill_flag);
 
+/* ---- IVFRABITQ, multi-bit codes (rabitq_ex_kernels.hpp; the code and the
+ * estimate are at the top of that file). nb_bits is 4 or 8; a bucket entry
+ * is d * nb_bits / 32 code words, then A and Mul as fp32
+ * (d * nb_bits / 8 + 8 bytes); `svals` holds sum_j u_j * c_j. Each entry
+ * has the contract of its 1-bit namesake above. */
+hipError_t rabitq_encode_ex(hipStream_t s, int nb_bits, int64_t n, int d,
+                            const float *x, const int32_t *asg, int asg_const,
+                            int nlist, const float *centroids, bool ip,
+                            uint8_t *entries, float *svals);
+hipError_t rabitq_sval_buckets_ex(hipStream_t s, int nb_bits, int nlist,
+                                  int d, const GammaBucketDev *bks,
+                                  const float *centroids);
+hipError_t rabitq_scan_ex(hipStream_t s, int nb_bits, int nq, int S, int d,
+                          int nprobe, int k2, const float *queries,
+                          const float *centroids,
+                          const GammaBucketDev *buckets, int nlist,
+                          const int64_t *probes, const uint32_t *bitmap,
+                          bool ip, uint64_t *out_keys, const int *kill_flag);
+
 }  // namespace gk
