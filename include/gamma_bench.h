@@ -271,44 +271,30 @@ int GammaKTestHammingFlatScan(int nq, int64_t n, int W, int k2,
                               const uint32_t *const *segs, int seg_shift,
                               const uint32_t *bitmap, uint64_t *out_keys);
 
-/* IVFRABITQ kernels (index_type "IVFRABITQ", nb_bits = 1; d % 32 == 0,
- * 32 <= d <= 4096). An entry is d/8 + 8 bytes: the sign bits (bit j of a
- * vector = (byte[j>>3] >> (j&7)) & 1), then the factors A and Mul as
- * little-endian fp32 — GammaDebugGetList serves the lists in this form,
- * code_size = d/8 + 8. RabitqEncode: x (n x d), asg (n list numbers; 0 =
- * every vector in list asg_const), centroids (nlist x d) -> entries
- * (n x (d/8 + 8) bytes) and svals (n floats, sum of the centroid's
- * coordinates under the set bits). RabitqScan has GammaKTestIvfpqScan's
- * bucket / probe / key layout with such entries and svals. */
-int GammaKTestRabitqEncode(int64_t n, int d, const float *x,
+/* IVFRABITQ kernels (index_type "IVFRABITQ", nb_bits = 1, 4 or 8;
+ * d % 32 == 0, 32 <= d <= 4096). An entry is d * nb_bits / 8 + 8 bytes: the
+ * codes, then the factors A and Mul as little-endian fp32 —
+ * GammaDebugGetList serves the lists in this form, code_size =
+ * d * nb_bits / 8 + 8. nb_bits 1: the sign bits (bit j of a vector =
+ * (byte[j>>3] >> (j&7)) & 1). nb_bits 4 / 8: the unsigned codes u_j (nb_bits
+ * 4: nibble j & 7 of little-endian 32-bit word j >> 3; nb_bits 8: byte j).
+ * RabitqEncode: x (n x d), asg (n list numbers; 0 = every vector in list
+ * asg_const), centroids (nlist x d) -> entries (n x code_size bytes) and
+ * svals (n floats: sum_j u_j * c_j over the centroid's coordinates, u_j the
+ * bit at nb_bits 1). RabitqScan has GammaKTestIvfpqScan's bucket / probe /
+ * key layout with such entries and svals. */
+int GammaKTestRabitqEncode(int nb_bits, int64_t n, int d, const float *x,
                            const int32_t *asg, int asg_const, int nlist,
                            const float *centroids, int ip, uint8_t *entries,
                            float *svals);
-int GammaKTestRabitqScan(int nq, int S, int d, int nprobe, int k2,
-                         const float *queries, const float *centroids,
-                         const void *buckets_dev, int nlist,
-                         const int64_t *probes, const uint32_t *bitmap,
-                         int ip, uint64_t *out_keys, const int *kill_flag);
-int GammaKTestRabitqSvalBuckets(int nlist, int d, const void *bks_dev,
-                                const float *centroids);
-/* The same three for nb_bits = 4 or 8. An entry is d * nb_bits / 8 + 8
- * bytes: the unsigned codes u_j (nb_bits 4: nibble j & 7 of little-endian
- * 32-bit word j >> 3; nb_bits 8: byte j), then A and Mul as little-endian
- * fp32; svals hold sum_j u_j * c_j. GammaDebugGetList serves the lists of
- * such a table in this form. */
-int GammaKTestRabitqEncodeEx(int nb_bits, int64_t n, int d, const float *x,
-                             const int32_t *asg, int asg_const, int nlist,
-                             const float *centroids, int ip,
-                             uint8_t *entries, float *svals);
-int GammaKTestRabitqScanEx(int nb_bits, int nq, int S, int d, int nprobe,
-                           int k2, const float *queries,
-                           const float *centroids, const void *buckets_dev,
-                           int nlist, const int64_t *probes,
-                           const uint32_t *bitmap, int ip,
-                           uint64_t *out_keys, const int *kill_flag);
-int GammaKTestRabitqSvalBucketsEx(int nb_bits, int nlist, int d,
-                                  const void *bks_dev,
-                                  const float *centroids);
+int GammaKTestRabitqScan(int nb_bits, int nq, int S, int d, int nprobe,
+                         int k2, const float *queries,
+                         const float *centroids, const void *buckets_dev,
+                         int nlist, const int64_t *probes,
+                         const uint32_t *bitmap, int ip, uint64_t *out_keys,
+                         const int *kill_flag);
+int GammaKTestRabitqSvalBuckets(int nb_bits, int nlist, int d,
+                                const void *bks_dev, const float *centroids);
 /* gk::coarse_select, the seed-filtered coarse assign (kernels.h): dots is
  * nq x nlist floats of scratch, cand nq x cap keys, cand_cnt nq + 1 ints
  * (per-query candidate counters, then the overflow flag), sel_keys the

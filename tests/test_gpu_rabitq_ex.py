@@ -74,8 +74,42 @@ def test_kernel_encode(B, D, ip):
 SIZES = [0, 1, 63, 64, 65] + BS_SIZES[2:] + [3 + (i % 5) for i in range(34)]
 
 
-@pytest.mark.parametrize("dyadic", [True, False])
-@pytest.mark.parametrize("D", [32, 96, 128, 288])
+def _encoded_lists(B, D, cent, ids, vecs, queries, marks, dyadic, ip):
+    """the encode kernel's entries of the lists in the scan hook's form
+    (ids carrying the delete marks), and per list the reference estimates
+    with their bounds: 2^-20 scale for dyadic inputs, else _sum_tol(D)"""
+    from vearch_amd import ktest
+    sizes = [len(i) for i in ids]
+    asg = np.repeat(np.arange(len(sizes)), sizes).astype(np.int32)
+    cut = np.cumsum(sizes)[:-1]
+    ent, sv = ktest.rabitq_encode(np.concatenate(vecs), asg, cent, ip,
+                                  nb_bits=B)
+    dev, tab = [], []
+    for ln, (e, s) in enumerate(zip(np.split(ent, cut), np.split(sv, cut))):
+        dev.append((np.where(marks[ln], ids[ln] | MARK32, ids[ln]), e, s))
+        u, A, Mul = rx.unpack(e, D, B)
+        sc = [rx.scale(q, cent[ln], A, Mul, B, ip) for q in queries]
+        tab.append((np.stack([rx.estimate(q, cent[ln], u, A, Mul, B, ip)
+                              for q in queries]),
+                    np.stack(sc) * (2.0 ** -20 if dyadic else _sum_tol(D))))
+    return dev, tab
+
+
+def _check_rows(keys, od, oi, tab, ids, marks, bm, probes, S, ip):
+    """raw partial rows against their sub-block's probes, merged rows
+    against all probes"""
+    for r in range(NQ_SCAN):
+        for s in range(S):
+            rr.check_row(*kr.key_decode(keys[r, s], ip),
+                         *_cands(tab, ids, marks, bm,
+                                 probes[r, s::S].tolist(), r), ip)
+        rr.check_row(od[r], oi[r],
+                     *_cands(tab, ids, marks, bm, probes[r].tolist(), r), ip)
+
+
+@pytest.mark.parametrize("D,dyadic",
+                         [(D, dy) for D in (32, 96, 128, 288)
+                          for dy in (True, False)] + [(64, True), (256, True)])
 @pytest.mark.parametrize("B", BITS)
 def test_kernel_scan(B, D, dyadic, monkeypatch):
     """Dyadic inputs (multiples of 1/16 in [-4, 4]): every sum the kernel
@@ -84,7 +118,9 @@ def test_kernel_scan(B, D, dyadic, monkeypatch):
     rabitq_ex_ref.tol. List sizes around the wave and both block sizes, 49
     probes (two chunks; one -1, one out of range), delete marks and a
     bitmap at ~30 % each; raw partial rows and rows merged by sort_rows.
-    The entries are the encode kernel's."""
+    The entries are the encode kernel's. Over both widths the D cover every
+    register-resident scan (4 bits: 64, 128, 256; 8 bits: 32, 64, 128) and
+    the streamed one."""
     from vearch_amd import ktest
     id_space = sum(SIZES) + 64
     cent, ids, vecs, queries, probes = _scan_case(D, 1000 * B + D, dyadic,
@@ -92,21 +128,9 @@ def test_kernel_scan(B, D, dyadic, monkeypatch):
     rng = np.random.default_rng(D)
     marks = [rng.random(n) < 0.3 for n in SIZES]
     bm = rng.random(id_space) < 0.3
-    asg = np.repeat(np.arange(len(SIZES)), SIZES).astype(np.int32)
-    cut = np.cumsum(SIZES)[:-1]
     for ip in METRICS:
-        ent, sv = ktest.rabitq_encode(np.concatenate(vecs), asg, cent, ip,
-                                      nb_bits=B)
-        dev, tab = [], []
-        for ln, (e, s) in enumerate(zip(np.split(ent, cut),
-                                        np.split(sv, cut))):
-            dev.append((np.where(marks[ln], ids[ln] | MARK32, ids[ln]), e, s))
-            u, A, Mul = rx.unpack(e, D, B)
-            sc = [rx.scale(q, cent[ln], A, Mul, B, ip) for q in queries]
-            tab.append((np.stack([rx.estimate(q, cent[ln], u, A, Mul, B, ip)
-                                  for q in queries]),
-                        np.stack(sc) * (2.0 ** -20 if dyadic
-                                        else _sum_tol(D))))
+        dev, tab = _encoded_lists(B, D, cent, ids, vecs, queries, marks,
+                                  dyadic, ip)
         for bs in (512, 256):
             monkeypatch.setenv("GAMMA_SCAN_BS", str(bs))
             for S, k2 in [(S, k2) for S in (1, 3) for k2 in (1, 10, 200)]:
@@ -114,14 +138,35 @@ def test_kernel_scan(B, D, dyadic, monkeypatch):
                     dev, probes, queries, cent, S, k2, ip,
                     bitmap=kr.bitmap_words(bm), kill_flag=True, nb_bits=B)
                 assert keys.shape == (NQ_SCAN, S, k2)
-                for r in range(NQ_SCAN):
-                    for s in range(S):
-                        rr.check_row(*kr.key_decode(keys[r, s], ip),
-                                     *_cands(tab, ids, marks, bm,
-                                             probes[r, s::S].tolist(), r), ip)
-                    rr.check_row(od[r], oi[r],
-                                 *_cands(tab, ids, marks, bm,
-                                         probes[r].tolist(), r), ip)
+                _check_rows(keys, od, oi, tab, ids, marks, bm, probes, S, ip)
+
+
+@pytest.mark.parametrize("B", BITS)
+def test_kernel_scan_kill_flag(B):
+    """test_gpu_rabitq.py's kill-flag test for the multi-bit widths: a flag
+    raised before the launch is read at the first chunk close, so every key
+    is EMPTY and every id -1; a flag left at 0 changes nothing. The 1-bit
+    test's lists (46 probes, two chunks at S = 1), dyadic, D = 32: streamed
+    at 4 bits, register-resident at 8."""
+    from vearch_amd import ktest
+    sizes = BS_SIZES + [3 + (i % 5) for i in range(34)]
+    cent, ids, vecs, queries, probes = _scan_case(32, 532 + B, True, sizes,
+                                                  int(sum(sizes)) + 64)
+    assert probes.shape[1] > 32
+    marks = [np.zeros(n, dtype=bool) for n in sizes]
+    for ip in METRICS:
+        dev, tab = _encoded_lists(B, 32, cent, ids, vecs, queries, marks,
+                                  True, ip)
+        for S, k2 in ((1, 10), (2, 1024)):
+            keys, _, oi = ktest.rabitq_scan(dev, probes, queries, cent, S,
+                                            k2, ip, kill_flag=1, nb_bits=B)
+            assert keys.shape == (NQ_SCAN, S, k2)
+            assert np.all(keys == np.uint64(kr.EMPTY)), (ip, S, k2)
+            assert np.all(oi == -1)
+            keys, od, oi = ktest.rabitq_scan(dev, probes, queries, cent, S,
+                                             k2, ip, kill_flag=0, nb_bits=B)
+            assert keys.shape == (NQ_SCAN, S, k2)
+            _check_rows(keys, od, oi, tab, ids, marks, None, probes, S, ip)
 
 
 # ------------------------------------------------------------------- engine

@@ -918,13 +918,9 @@ int IVFIndex::pq_subspace_kmeans_(const float *sub_host, int64_t n,
 hipError_t IVFIndex::rabitq_encode_(hipStream_t s, int64_t n, const float *x,
                                     const int32_t *asg, uint8_t *entries,
                                     float *svals) {
-  if (params_.nb_bits == 1)
-    return gk::rabitq_encode(s, n, d_, x, asg, 0, nlist_,
-                             centroids_.as<float>(), params_.metric_ip,
-                             entries, svals);
-  return gk::rabitq_encode_ex(s, params_.nb_bits, n, d_, x, asg, 0, nlist_,
-                              centroids_.as<float>(), params_.metric_ip,
-                              entries, svals);
+  return gk::rabitq_encode(s, params_.nb_bits, n, d_, x, asg, 0, nlist_,
+                           centroids_.as<float>(), params_.metric_ip, entries,
+                           svals);
 }
 
 /* residuals -> bucket-format entries (code_size_ bytes each) */
@@ -967,8 +963,7 @@ int IVFIndex::add(const float *x_host, const int64_t *vids, int64_t n,
                   hipStream_t s) {
   if (!trained_ || n <= 0) return trained_ ? 0 : -1;
   const int64_t chunk = 65536;
-  const size_t entry =
-      coded() ? (size_t)code_size_ : (size_t)d_ * 4;
+  const size_t entry = entry_bytes();
 
   DeviceBuf xd, xnorm, dots, asg, resid, codes, sterm;
   std::vector<int32_t> asg_h(std::min(n, chunk));
@@ -1230,7 +1225,7 @@ int IVFIndex::commit_fast_one(int32_t b, int64_t vid, const float *vec_h,
   Bucket &bk = buckets_[b];
   if (bk.size + 1 > bk.cap) return -1; /* prepare checked; appenders
                                           are serialized */
-  const size_t entry = coded() ? (size_t)code_size_ : (size_t)d_ * 4;
+  const size_t entry = entry_bytes();
   /* data first ... */
   if (coded()) {
     GAMMA_CHECK(hipMemcpy((uint8_t *)bk.data->get() +
@@ -1298,7 +1293,7 @@ int IVFIndex::compact(float min_ratio, const uint32_t *bitmap_dev,
                       hipStream_t s, CompactStats *st) {
   if (!trained_ || !compactable(min_ratio)) return 0;
   const bool pq = coded(); /* code bytes + sval per entry */
-  const size_t entry = pq ? (size_t)code_size_ : (size_t)d_ * 4;
+  const size_t entry = entry_bytes();
   std::vector<int> sel;
   for (int b = 0; b < nlist_; b++)
     if (bucket_compactable_(b, min_ratio)) sel.push_back(b);
@@ -1605,18 +1600,11 @@ int IVFIndex::search(const float *q_dev, int nq, int k2, int nprobe,
     /* the factor A in the entries was encoded for the table's metric; a
      * request that overrides the metric is served as IVFPQ serves it, in
      * the requested key order over the codes as they are */
-    if (params_.nb_bits == 1)
-      GAMMA_CHECK(gk::rabitq_scan(s, nq, S, d_, nprobe, k2, q_dev,
-                                  centroids_.as<float>(),
-                                  dev_buckets_.as<GammaBucketDev>(), nlist_,
-                                  sc.probes.as<int64_t>(), bitmap_dev,
-                                  metric_ip, out_keys_dev, kill_flag_dev));
-    else
-      GAMMA_CHECK(gk::rabitq_scan_ex(
-          s, params_.nb_bits, nq, S, d_, nprobe, k2, q_dev,
-          centroids_.as<float>(), dev_buckets_.as<GammaBucketDev>(), nlist_,
-          sc.probes.as<int64_t>(), bitmap_dev, metric_ip, out_keys_dev,
-          kill_flag_dev));
+    GAMMA_CHECK(gk::rabitq_scan(
+        s, params_.nb_bits, nq, S, d_, nprobe, k2, q_dev,
+        centroids_.as<float>(), dev_buckets_.as<GammaBucketDev>(), nlist_,
+        sc.probes.as<int64_t>(), bitmap_dev, metric_ip, out_keys_dev,
+        kill_flag_dev));
   } else if (binary()) {
     GAMMA_CHECK(gk::binivf_scan(s, nq, S, d_, nprobe, k2,
                                 (const uint32_t *)q_dev,
@@ -1648,8 +1636,7 @@ int IVFIndex::copy_list_to_host(int64_t ln, int64_t *ids, uint8_t *codes,
                                 hipStream_t s) const {
   if (ln < 0 || ln >= nlist_) return -1;
   const Bucket &bk = buckets_[ln];
-  const size_t entry =
-      coded() ? (size_t)code_size_ : (size_t)d_ * 4;
+  const size_t entry = entry_bytes();
   if (bk.size == 0) return 0;
   if (ids) {
     std::vector<uint32_t> tmp(bk.size);
@@ -1702,8 +1689,7 @@ int IVFIndex::dump(FILE *f, hipStream_t s) const {
     int hdr[2] = {params_.nb_bits, params_.metric_ip ? 1 : 0};
     fwrite(hdr, 4, 2, f);
   }
-  const size_t entry =
-      coded() ? (size_t)code_size_ : (size_t)d_ * 4;
+  const size_t entry = entry_bytes();
   fwrite(&ntotal_, 8, 1, f);
   for (int i = 0; i < nlist_; i++) {
     long long sz = buckets_[i].size;
@@ -1771,8 +1757,7 @@ int IVFIndex::load(FILE *f, hipStream_t s, std::string *err) {
       return -1;
     }
   }
-  const size_t entry =
-      coded() ? (size_t)code_size_ : (size_t)d_ * 4;
+  const size_t entry = entry_bytes();
   if (fread(&ntotal_, 8, 1, f) != 1) return -1;
   for (int i = 0; i < nlist_; i++) {
     long long sz = 0;
@@ -1834,14 +1819,9 @@ int IVFIndex::load(FILE *f, hipStream_t s, std::string *err) {
       return -1;
     GAMMA_CHECK(hipStreamSynchronize(s));
   } else if (rabitq()) {
-    if ((params_.nb_bits == 1
-             ? gk::rabitq_sval_buckets(s, nlist_, d_,
-                                       dev_buckets_.as<GammaBucketDev>(),
-                                       centroids_.as<float>())
-             : gk::rabitq_sval_buckets_ex(s, params_.nb_bits, nlist_, d_,
-                                          dev_buckets_.as<GammaBucketDev>(),
-                                          centroids_.as<float>())) !=
-        hipSuccess)
+    if (gk::rabitq_sval_buckets(s, params_.nb_bits, nlist_, d_,
+                                dev_buckets_.as<GammaBucketDev>(),
+                                centroids_.as<float>()) != hipSuccess)
       return -1;
     GAMMA_CHECK(hipStreamSynchronize(s));
   }

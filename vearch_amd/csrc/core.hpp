@@ -202,8 +202,7 @@ class Bitmap {
  * like IVFPQ — raw store, k-means, GEMM coarse assign and the exact re-rank
  * leg are shared — with list entries of d * nb_bits / 8 + 8 code bytes (the
  * codes, then the factors A and Mul) plus one device-only sval per entry,
- * the shape of an IVFPQ entry. See rabitq_kernels.hpp (1 bit) and
- * rabitq_ex_kernels.hpp (4 and 8 bits). */
+ * the shape of an IVFPQ entry. See rabitq_kernels.hpp. */
 enum class IndexKind { FLAT, IVFPQ, IVFFLAT, BINARYIVF, IVFRABITQ };
 
 struct IndexParams {
@@ -276,8 +275,13 @@ class IVFIndex {
   bool coded() const {
     return params_.kind == IndexKind::IVFPQ || rabitq();
   }
-  /* IVFRABITQ dimension bound: the scan's LDS holds 20 d bytes of query
-   * table and query next to 25 KB of selector and chunk state */
+  /* bytes of one bucket entry */
+  size_t entry_bytes() const {
+    return coded() ? (size_t)code_size_ : (size_t)d_ * 4;
+  }
+  /* IVFRABITQ dimension bound: the scan's LDS holds 4 d bytes of query and,
+   * at nb_bits 1, 16 d bytes of query table next to 25 KB of selector and
+   * chunk state */
   static constexpr int kRabitqMaxDim = 4096;
   /* IVFPQ: cap on the per-search query-table scratch (SearchScratch::atab,
    * nsubvector KB per query at 8 bits); search() walks larger batches in
@@ -379,7 +383,7 @@ class IVFIndex {
                           int seed_off);
   int encode_entries_(hipStream_t s, int64_t n, const float *resid,
                       uint8_t *codes);
-  /* IVFRABITQ: gk::rabitq_encode or, for nb_bits 4 / 8, rabitq_encode_ex */
+  /* IVFRABITQ: gk::rabitq_encode of the table's nb_bits, list numbers asg */
   hipError_t rabitq_encode_(hipStream_t s, int64_t n, const float *x,
                             const int32_t *asg, uint8_t *entries,
                             float *svals);

@@ -366,22 +366,24 @@ hipError_t hamming_flat_scan(hipStream_t s, int nq, int64_t n, int W, int k2,
                              const uint32_t *const *segs, int seg_shift,
                              const uint32_t *bitmap, uint64_t *out_keys);
 
-/* ---- IVFRABITQ (rabitq_kernels.hpp; the maths is at the top of that
- * file). d % 32 == 0, 32 <= d <= 4096. A bucket entry is d/32 sign words,
- * then the factors A and Mul as fp32 (d/8 + 8 bytes); bucket `svals` holds
- * sum_j bit_j * c_j of the entry's list centroid c. */
+/* ---- IVFRABITQ (rabitq_kernels.hpp; the codes and the estimates are at
+ * the top of that file). nb_bits is 1, 4 or 8; d % 32 == 0, 32 <= d <= 4096.
+ * A bucket entry is d * nb_bits / 32 code words (nb_bits 1: the sign
+ * words), then the factors A and Mul as fp32 (d * nb_bits / 8 + 8 bytes);
+ * bucket `svals` holds sum_j u_j * c_j of the entry's list centroid c
+ * (nb_bits 1: u_j = bit_j). */
 
 /* entries[i], svals[i] of vector x_i in list asg[i] (asg null: every
  * vector in list asg_const; numbers outside [0, nlist) are clamped).
  * ip selects A = n2 - ||x||^2 instead of n2. Deterministic: fixed
  * summation order, so equal inputs give equal bytes. */
-hipError_t rabitq_encode(hipStream_t s, int64_t n, int d, const float *x,
-                         const int32_t *asg, int asg_const, int nlist,
-                         const float *centroids, bool ip, uint8_t *entries,
-                         float *svals);
+hipError_t rabitq_encode(hipStream_t s, int nb_bits, int64_t n, int d,
+                         const float *x, const int32_t *asg, int asg_const,
+                         int nlist, const float *centroids, bool ip,
+                         uint8_t *entries, float *svals);
 /* Load path: rebuild every bucket's svals from its entries and centroid
  * in one launch, bit-identical to rabitq_encode's. */
-hipError_t rabitq_sval_buckets(hipStream_t s, int nlist, int d,
+hipError_t rabitq_sval_buckets(hipStream_t s, int nb_bits, int nlist, int d,
                                const GammaBucketDev *bks,
                                const float *centroids);
 /* RaBitQ IVF fused scan, the contract of ivfpq_scan / binivf_scan: one
@@ -390,32 +392,14 @@ hipError_t rabitq_sval_buckets(hipStream_t s, int nlist, int d,
  * skipped; bit 31 of an id and the bitmap drop an entry; kill_flag
  * (optional) stops the scan. Keys are gamma_make_key<ip> of the estimate
  * (L2 ascending / inner product descending, ties by id). The kernel builds
- * its query table and the per-probe scalars itself from queries and
- * centroids. k2 <= 1024. Reads GAMMA_SCAN_BS; scores do not depend on it
- * or on S. */
-hipError_t rabitq_scan(hipStream_t s, int nq, int S, int d, int nprobe,
-                       int k2, const float *queries, const float *centroids,
-                       const GammaBucketDev *buckets, int nlist,
-                       const int64_t *probes, const uint32_t *bitmap, bool ip,
-                       uint64_t *out_keys, const int *kill_flag);
-
-/* ---- IVFRABITQ, multi-bit codes (rabitq_ex_kernels.hpp; the code and the
- * estimate are at the top of that file). nb_bits is 4 or 8; a bucket entry
- * is d * nb_bits / 32 code words, then A and Mul as fp32
- * (d * nb_bits / 8 + 8 bytes); `svals` holds sum_j u_j * c_j. Each entry
- * has the contract of its 1-bit namesake above. */
-hipError_t rabitq_encode_ex(hipStream_t s, int nb_bits, int64_t n, int d,
-                            const float *x, const int32_t *asg, int asg_const,
-                            int nlist, const float *centroids, bool ip,
-                            uint8_t *entries, float *svals);
-hipError_t rabitq_sval_buckets_ex(hipStream_t s, int nb_bits, int nlist,
-                                  int d, const GammaBucketDev *bks,
-                                  const float *centroids);
-hipError_t rabitq_scan_ex(hipStream_t s, int nb_bits, int nq, int S, int d,
-                          int nprobe, int k2, const float *queries,
-                          const float *centroids,
-                          const GammaBucketDev *buckets, int nlist,
-                          const int64_t *probes, const uint32_t *bitmap,
-                          bool ip, uint64_t *out_keys, const int *kill_flag);
+ * its query table (nb_bits 1) and the per-probe scalars itself from
+ * queries and centroids. k2 <= 1024. Reads GAMMA_SCAN_BS; scores do not
+ * depend on it or on S. */
+hipError_t rabitq_scan(hipStream_t s, int nb_bits, int nq, int S, int d,
+                       int nprobe, int k2, const float *queries,
+                       const float *centroids, const GammaBucketDev *buckets,
+                       int nlist, const int64_t *probes,
+                       const uint32_t *bitmap, bool ip, uint64_t *out_keys,
+                       const int *kill_flag);
 
 }  // namespace gk

@@ -1577,8 +1577,5 @@ hipError_t gk::pq_encode_pack4(hipStream_t s, int64_t n, int d, int M,
 /* BINARYIVF: Hamming matrix, list scan, flat scan */
 #include "binary_kernels.hpp"
 
-/* IVFRABITQ: encode, sval rebuild, list scan */
+/* IVFRABITQ, nb_bits 1, 4 and 8: encode, sval rebuild, list scan */
 #include "rabitq_kernels.hpp"
-
-/* IVFRABITQ, nb_bits 4 and 8: the same three, table-free scan */
-#include "rabitq_ex_kernels.hpp"

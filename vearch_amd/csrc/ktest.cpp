@@ -246,61 +246,34 @@ int GammaKTestHammingFlatScan(int nq, int64_t n, int W, int k2,
                                        seg_shift, bitmap, out_keys));
 }
 
-int GammaKTestRabitqEncode(int64_t n, int d, const float *x,
+int GammaKTestRabitqEncode(int nb_bits, int64_t n, int d, const float *x,
                            const int32_t *asg, int asg_const, int nlist,
                            const float *centroids, int ip, uint8_t *entries,
                            float *svals) {
-  return kt_done(gk::rabitq_encode(nullptr, n, d, x, asg, asg_const, nlist,
-                                   centroids, ip != 0, entries, svals));
+  return kt_done(gk::rabitq_encode(nullptr, nb_bits, n, d, x, asg, asg_const,
+                                   nlist, centroids, ip != 0, entries,
+                                   svals));
 }
 
-int GammaKTestRabitqScan(int nq, int S, int d, int nprobe, int k2,
-                         const float *queries, const float *centroids,
-                         const void *buckets_dev, int nlist,
-                         const int64_t *probes, const uint32_t *bitmap,
-                         int ip, uint64_t *out_keys, const int *kill_flag) {
-  return kt_done(gk::rabitq_scan(nullptr, nq, S, d, nprobe, k2, queries,
-                                 centroids,
+int GammaKTestRabitqScan(int nb_bits, int nq, int S, int d, int nprobe,
+                         int k2, const float *queries,
+                         const float *centroids, const void *buckets_dev,
+                         int nlist, const int64_t *probes,
+                         const uint32_t *bitmap, int ip, uint64_t *out_keys,
+                         const int *kill_flag) {
+  return kt_done(gk::rabitq_scan(nullptr, nb_bits, nq, S, d, nprobe, k2,
+                                 queries, centroids,
                                  (const GammaBucketDev *)buckets_dev, nlist,
                                  probes, bitmap, ip != 0, out_keys,
                                  kill_flag));
 }
 
-int GammaKTestRabitqSvalBuckets(int nlist, int d, const void *bks_dev,
+int GammaKTestRabitqSvalBuckets(int nb_bits, int nlist, int d,
+                                const void *bks_dev,
                                 const float *centroids) {
-  return kt_done(gk::rabitq_sval_buckets(nullptr, nlist, d,
+  return kt_done(gk::rabitq_sval_buckets(nullptr, nb_bits, nlist, d,
                                          (const GammaBucketDev *)bks_dev,
                                          centroids));
-}
-
-int GammaKTestRabitqEncodeEx(int nb_bits, int64_t n, int d, const float *x,
-                             const int32_t *asg, int asg_const, int nlist,
-                             const float *centroids, int ip,
-                             uint8_t *entries, float *svals) {
-  return kt_done(gk::rabitq_encode_ex(nullptr, nb_bits, n, d, x, asg,
-                                      asg_const, nlist, centroids, ip != 0,
-                                      entries, svals));
-}
-
-int GammaKTestRabitqScanEx(int nb_bits, int nq, int S, int d, int nprobe,
-                           int k2, const float *queries,
-                           const float *centroids, const void *buckets_dev,
-                           int nlist, const int64_t *probes,
-                           const uint32_t *bitmap, int ip,
-                           uint64_t *out_keys, const int *kill_flag) {
-  return kt_done(gk::rabitq_scan_ex(nullptr, nb_bits, nq, S, d, nprobe, k2,
-                                    queries, centroids,
-                                    (const GammaBucketDev *)buckets_dev,
-                                    nlist, probes, bitmap, ip != 0, out_keys,
-                                    kill_flag));
-}
-
-int GammaKTestRabitqSvalBucketsEx(int nb_bits, int nlist, int d,
-                                  const void *bks_dev,
-                                  const float *centroids) {
-  return kt_done(gk::rabitq_sval_buckets_ex(nullptr, nb_bits, nlist, d,
-                                            (const GammaBucketDev *)bks_dev,
-                                            centroids));
 }
 
 int GammaKTestCoarseSelect(const float *Q, int nq, const float *B,

@@ -65,9 +65,10 @@ def _lib():
         L.GammaKTestHammingFlatScan.argtypes = [
             i32, i64, i32, i32, vp, vp, i32, vp, vp]
         L.GammaKTestRabitqEncode.argtypes = [
-            i64, i32, vp, vp, i32, i32, vp, i32, vp, vp]
+            i32, i64, i32, vp, vp, i32, i32, vp, i32, vp, vp]
         L.GammaKTestRabitqScan.argtypes = [
-            i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp]
+            i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, i32, vp,
+            vp]
         L.GammaKTestIvfflatScan.argtypes = [
             i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp]
         L.GammaKTestPqTablesB.argtypes = [i32, i32, i32, i32, vp, vp, vp]
@@ -78,13 +79,7 @@ def _lib():
         L.GammaKTestResiduals.argtypes = [i64, i32, vp, vp, vp, vp]
         L.GammaKTestRowNorms.argtypes = [vp, i64, i32, vp]
         L.GammaKTestExtractProbe0.argtypes = [i32, i32, vp, vp]
-        L.GammaKTestRabitqSvalBuckets.argtypes = [i32, i32, vp, vp]
-        L.GammaKTestRabitqEncodeEx.argtypes = [
-            i32, i64, i32, vp, vp, i32, i32, vp, i32, vp, vp]
-        L.GammaKTestRabitqScanEx.argtypes = [
-            i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, i32, vp,
-            vp]
-        L.GammaKTestRabitqSvalBucketsEx.argtypes = [i32, i32, i32, vp, vp]
+        L.GammaKTestRabitqSvalBuckets.argtypes = [i32, i32, i32, vp, vp]
         L.GammaKTestCoarseSelect.argtypes = [
             vp, i32, vp, i64, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp,
             vp, vp]
@@ -750,20 +745,15 @@ def pq_sterm_buckets(buckets, btab, M, ksub, skip=()):
 
 
 def rabitq_sval_buckets(buckets, centroids, skip=(), nb_bits=1):
-    """gk::rabitq_sval_buckets (nb_bits 4 / 8: rabitq_sval_buckets_ex):
-    bucket li holds entries of d * nb_bits / 8 + 8 bytes of list li,
-    centroids float32 (nlist, d). See _sval_buckets."""
+    """gk::rabitq_sval_buckets: bucket li holds entries of
+    d * nb_bits / 8 + 8 bytes of list li, centroids float32 (nlist, d). See _sval_buckets."""
     c_d = _f32_dev(centroids)
     nlist, d = c_d.shape
     assert nlist == len(buckets) and d % 32 == 0
 
     def hook(bk_d, nl):
-        if nb_bits == 1:
-            _call("GammaKTestRabitqSvalBuckets", nl, d,
-                  _p(bk_d, torch.int64), _p(c_d))
-        else:
-            _call("GammaKTestRabitqSvalBucketsEx", nb_bits, nl, d,
-                  _p(bk_d, torch.int64), _p(c_d))
+        _call("GammaKTestRabitqSvalBuckets", nb_bits, nl, d,
+              _p(bk_d, torch.int64), _p(c_d))
     return _sval_buckets(hook, buckets, d * nb_bits // 8 + 8, skip)
 
 
@@ -932,11 +922,10 @@ def hamming_flat_scan(queries, base, seg_shift, k2, bitmap=None):
 
 # ------------------------------------------------------------ IVFRABITQ
 def rabitq_encode(x, asg, centroids, ip, nb_bits=1):
-    """One gk::rabitq_encode launch (nb_bits 4 / 8: rabitq_encode_ex) on
-    host arrays: x float32 (n, d), asg int32 (n,) list numbers, centroids
-    float32 (nlist, d), d % 32 == 0 -> (entries uint8 (n, d * nb_bits / 8 +
-    8), svals float32 (n,)) numpy. Outputs are pre-filled (0xEE / nan) so an
-    unwritten byte is visible."""
+    """One gk::rabitq_encode launch on host arrays: x float32 (n, d), asg
+    int32 (n,) list numbers, centroids float32 (nlist, d), d % 32 == 0 ->
+    (entries uint8 (n, d * nb_bits / 8 + 8), svals float32 (n,)) numpy.
+    Outputs are pre-filled (0xEE / nan) so an unwritten byte is visible."""
     f32 = lambda a: torch.from_numpy(  # noqa: E731
         np.ascontiguousarray(a, dtype=np.float32).copy()).cuda()
     x_d, c_d = f32(x), f32(centroids)
@@ -949,19 +938,17 @@ def rabitq_encode(x, asg, centroids, ip, nb_bits=1):
     ent = torch.full((n, d * nb_bits // 8 + 8), 0xEE, dtype=torch.uint8,
                      device="cuda")
     sv = torch.full((n,), float("nan"), dtype=torch.float32, device="cuda")
-    ex = () if nb_bits == 1 else (nb_bits,)
-    _call("GammaKTestRabitqEncode" + ("Ex" if ex else ""), *ex, n, d,
-          _p(x_d), _p(a_d, torch.int32), 0, nlist, _p(c_d), int(bool(ip)),
+    _call("GammaKTestRabitqEncode", nb_bits, n, d, _p(x_d),
+          _p(a_d, torch.int32), 0, nlist, _p(c_d), int(bool(ip)),
           _p(ent), _p(sv))
     return ent.cpu().numpy(), sv.cpu().numpy()
 
 
 def rabitq_scan(lists, probes, queries, centroids, S, k2, ip, bitmap=None,
                 kill_flag=False, nb_bits=1):
-    """One gk::rabitq_scan launch (nb_bits 4 / 8: rabitq_scan_ex) on host
-    arrays. lists: one (ids uint32 (n,), entries uint8 (n, d * nb_bits / 8
-    + 8), svals float32 (n,)) per inverted list
-    (n = 0 is legal), each array in its own device allocation; probes int64
+    """One gk::rabitq_scan launch on host arrays. lists: one (ids uint32
+    (n,), entries uint8 (n, d * nb_bits / 8 + 8), svals float32 (n,)) per
+    inverted list (n = 0 is legal), each array in its own device allocation; probes int64
     (nq, nprobe) may hold -1 and ids >= nlist; queries float32 (nq, d);
     centroids float32 (nlist, d); bitmap: optional uint32 words; kill_flag:
     see _kill_dev.
@@ -995,9 +982,8 @@ def rabitq_scan(lists, probes, queries, centroids, S, k2, ip, bitmap=None,
     kf_d = _kill_dev(kill_flag)
     keys = torch.full((nq, S, k2), 0x5A5A5A5A5A5A5A5A, dtype=torch.int64,
                       device="cuda")
-    ex = () if nb_bits == 1 else (nb_bits,)
-    _call("GammaKTestRabitqScan" + ("Ex" if ex else ""), *ex, nq, S, d,
-          nprobe, k2, _p(q_d), _p(c_d),
+    _call("GammaKTestRabitqScan", nb_bits, nq, S, d, nprobe, k2, _p(q_d),
+          _p(c_d),
           _p(bk_d, torch.int64), nlist, _p(pr_d, torch.int64),
           _p(bm_d, torch.int32), int(bool(ip)), _p(keys, torch.int64),
           _p(kf_d, torch.int32))
