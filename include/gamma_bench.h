@@ -138,6 +138,14 @@ int GammaKTestSelectFromDots(int nq, int64_t ncols, int64_t col_base,
                              const float *qnorms, const float *bnorms,
                              int l2, int ip_order, const uint32_t *bitmap,
                              int k2, uint64_t *state_keys, int seeded);
+/* select_from_dots with its wave_stats argument (k2 <= 192): stats is
+ * 2 * nq ints the caller zeroed */
+int GammaKTestSelectWaveStats(int nq, int64_t ncols, int64_t col_base,
+                              int64_t ld, const float *dots,
+                              const float *qnorms, const float *bnorms,
+                              int l2, int ip_order, const uint32_t *bitmap,
+                              int k2, uint64_t *state_keys, int seeded,
+                              int *stats);
 int GammaKTestSelectRowsFull(int nq, int ncols, int64_t ld,
                              const float *dots, const float *qnorms,
                              const float *bnorms, int l2, int ip_order,

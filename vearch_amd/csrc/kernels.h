@@ -102,13 +102,23 @@ hipError_t row_norms(hipStream_t s, const float *v, int64_t n, int d,
 /* Exact top-k2 select per row of a dots matrix.
  * dist = l2 ? (qn[q] + bn[col_base+c] - 2*dot) : dot; id = col_base + c.
  * bitmap: optional delete bitmap over global ids (u32 words).
- * state_keys (nq x k2 u64) is seeded from itself when `seeded`. */
+ * state_keys (nq x k2 u64) is seeded from itself when `seeded`.
+ * k2 <= 192 takes the wave-per-query kernel, which first bounds each row's
+ * k2-th key by the k2-th smallest of its group minima and primes the
+ * selector with it (DESIGN.md "Kernels" 2), for rows of at most 16384
+ * columns and while the seeds are fewer than k2; GAMMA_SELECT_PRIME=0,
+ * read per call, keeps the unprimed walk. Same result either way.
+ * wave_stats (optional, device, 2 * nq ints zeroed by the caller; kernel
+ * test hook only, k2 <= 192, no run_if): per query, the keys the walk
+ * admitted to the selector's append region and its flushes before the
+ * closing one. */
 hipError_t select_from_dots(hipStream_t s, int nq, int64_t ncols,
                             int64_t col_base, int64_t ld, const float *dots,
                             const float *qnorms, const float *bnorms,
                             bool l2, bool ip_order, const uint32_t *bitmap,
                             int k2, uint64_t *state_keys, bool seeded,
-                            const int *run_if = nullptr);
+                            const int *run_if = nullptr,
+                            int *wave_stats = nullptr);
 
 /* Coarse assign without the nq x nlist round trip (DESIGN.md "Kernels"
  * (a2)): sel_keys (nq x nprobe u64, sorted) = exact top-nprobe of

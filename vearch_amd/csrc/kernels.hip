@@ -350,21 +350,114 @@ k_select_from_dots(int nq, int64_t ncols, int64_t col_base, int64_t ld,
     state_keys[(int64_t)q * k2 + i] = res[i];
 }
 
+/* One walk of a wave over its row: visit(key, slot) for every live column,
+ * pass_end(margin) after each pass of at most `margin` keys per wave. The
+ * slot is a compile-time constant at every call after unrolling.
+ *   vector path: lane L of pass p holds columns 4 * (64 p + L) + t, t is
+ *     the slot (quarters the serial trip count over a 16k-wide row:
+ *     nlist=16384 coarse assign reads 64 KB/query; the scalar loop was
+ *     latency-bound);
+ *   scalar path: lane L of pass p holds column 64 p + L, p & 3 is the slot. */
+template <bool IP, class Visit, class PassEnd>
+__device__ __forceinline__ void
+gamma_walk_row(const float *__restrict__ row, int64_t ncols, int64_t col_base,
+               int lane, float qn, const float *__restrict__ bnorms, int l2,
+               const uint32_t *__restrict__ bitmap, Visit visit,
+               PassEnd pass_end) {
+  if ((ncols & 3) == 0 && (col_base & 3) == 0 && ((uintptr_t)row & 15) == 0) {
+    const float4 *row4 = (const float4 *)row;
+    for (int64_t c0 = 0; c0 < (ncols >> 2); c0 += 64) {
+      int64_t c4 = c0 + lane;
+      if (c4 < (ncols >> 2)) {
+        int64_t id0 = col_base + c4 * 4;
+        float4 d4 = row4[c4];
+        float4 b4 = l2 ? *(const float4 *)(bnorms + id0)
+                       : make_float4(0, 0, 0, 0);
+        float dv[4] = {d4.x, d4.y, d4.z, d4.w};
+        float bv[4] = {b4.x, b4.y, b4.z, b4.w};
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+          int64_t id = id0 + t;
+          if (!gamma_bitmap_test(bitmap, (uint64_t)id)) {
+            float dist = l2 ? fmaf(-2.0f, dv[t], qn + bv[t]) : dv[t];
+            visit(gamma_make_key<IP>(dist, (uint32_t)id), t);
+          }
+        }
+      }
+      pass_end(64 * 4);
+    }
+  } else {
+    for (int64_t c0 = 0; c0 < ncols; c0 += 4 * 64) {
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        if (c0 + u * 64 >= ncols) break;
+        int64_t c = c0 + u * 64 + lane;
+        if (c < ncols) {
+          int64_t id = col_base + c;
+          if (!gamma_bitmap_test(bitmap, (uint64_t)id)) {
+            float dot = row[c];
+            float dist = l2 ? fmaf(-2.0f, dot, qn + bnorms[id]) : dot;
+            visit(gamma_make_key<IP>(dist, (uint32_t)id), u);
+          }
+        }
+        pass_end(64);
+      }
+    }
+  }
+}
+
 /* Wave-per-query variant for small k2 (coarse assign: k2 = nprobe).
  * One block-wide selector per 4096-float row is barrier-dominated (it
  * measured 490 us/step, reading 164 MB at 334 GB/s); here each of the
  * 8 waves in a WG owns one query with a private GammaWaveSelector, so
- * the scan has no block barriers at all and flushes are rare (expected
- * pushes per wave ~ k2 * ln(ncols/k2)). Exact: same key order as the
- * block path (both validated against each other in tests). */
-template <bool IP>
+ * the scan has no block barriers at all. Exact: same key order as the
+ * block path (both validated against each other in tests).
+ *
+ * The row is walked twice. An unprimed selector admits every key of its
+ * first passes and pays wave-wide sorts of 512 slots for them, whatever
+ * the row width. So the first walk only takes minima: the row's columns
+ * fall into G = 64 * R disjoint groups (lane x slot & (R - 1), slots as
+ * in gamma_walk_row) and each lane keeps the smallest key of each of its
+ * R groups. tau = the k2-th smallest of the G minima: k2 distinct keys of
+ * the row are <= tau, hence so is the row's k2-th smallest, and the
+ * second walk (the selector, primed with tau) loses nothing by admitting
+ * only keys <= tau. Fewer than k2 live groups: tau = EMPTY, unprimed.
+ * With g = ncols / G columns per group tau sits at the key quantile p of
+ * G * (1 - (1 - p)^g) = k2, and about p * ncols keys are admitted.
+ * G = k2 is loose (tau = the largest minimum), and ranking costs
+ * 64 * R * R compares per lane, so R is the least of 1, 2, 4 with
+ * G >= 2 * k2:   k2 <= 32: R = 1;  k2 <= 64: R = 2;  k2 <= 128: R = 4.
+ * k2 in 129..192 also takes R = 4 (G = 256 >= 1.33 * k2; at k2 = 192 and
+ * 4096 columns the formula gives about 340 admitted keys, derived, not
+ * measured, where the unprimed walk sorts on every pass). Every k2 this
+ * kernel takes is served.
+ * The first walk runs only where it can pay (one wave-uniform test):
+ *  - the selector has no real threshold yet. A seeded selector that holds
+ *    k2 real keys already admits only keys below the running k2-th; the
+ *    minima of one more segment are almost never tighter than that (FLAT
+ *    accumulates 65536-column chunks this way). Seeds fewer than k2 leave
+ *    the threshold EMPTY and the walk is primed.
+ *  - ncols <= GAMMA_SELECT_PRIME_MAX_COLS. What priming saves is about
+ *    two 512-slot sorts per row, a fixed 19 ns per row on MI355X (0.19 ms
+ *    per 10 000 rows traced); what it costs is a second read of the row.
+ *    Rows of 16 KB (measured) to 64 KB come back out of L2 / Infinity
+ *    Cache right behind the first read; a wider row (a 256 KB FLAT chunk
+ *    row, 2.6 GB per launch) comes from HBM, and at 3-4 TB/s 64 KB per
+ *    row already costs the 16-22 ns that the sorts do.
+ * prime = 0 (GAMMA_SELECT_PRIME=0) skips the first walk everywhere.
+ * COUNT (test hook only): stats[2q] += keys admitted to the append region
+ * by the second walk, stats[2q + 1] = flushes before finish(). */
+#define GAMMA_SELECT_PRIME_MAX_COLS 16384 /* 64 KB of floats per row */
+
+template <bool IP, bool COUNT>
 __device__ __forceinline__ void
 gamma_select_wave(char *smem, int nq, int64_t ncols, int64_t col_base,
                   int64_t ld, const float *__restrict__ dots,
                   const float *__restrict__ qnorms,
                   const float *__restrict__ bnorms, int l2,
                   const uint32_t *__restrict__ bitmap, int k2,
-                  uint64_t *__restrict__ state_keys, int seeded) {
+                  uint64_t *__restrict__ state_keys, int seeded, int prime,
+                  int *__restrict__ stats) {
   const int nw = 512 / 64;
   uint64_t *wb = (uint64_t *)smem;
   int *cnts = (int *)(wb + (size_t)nw * GAMMA_WSEL_CAP);
@@ -386,48 +479,48 @@ gamma_select_wave(char *smem, int nq, int64_t ncols, int64_t col_base,
     }
     sel.finish();
   }
-  if ((ncols & 3) == 0 && (col_base & 3) == 0 && ((uintptr_t)row & 15) == 0) {
-    /* vectorized: 4 dists (and 4 bnorms) per lane per pass — quarters
-     * the serial trip count over a 16k-wide row (nlist=16384 coarse
-     * assign reads 64 KB/query; the scalar loop was latency-bound) */
-    const float4 *row4 = (const float4 *)row;
-    for (int64_t c0 = 0; c0 < (ncols >> 2); c0 += 64) {
-      int64_t c4 = c0 + lane;
-      if (c4 < (ncols >> 2)) {
-        int64_t id0 = col_base + c4 * 4;
-        float4 d4 = row4[c4];
-        float4 b4 = l2 ? *(const float4 *)(bnorms + id0)
-                       : make_float4(0, 0, 0, 0);
-        float dv[4] = {d4.x, d4.y, d4.z, d4.w};
-        float bv[4] = {b4.x, b4.y, b4.z, b4.w};
-#pragma unroll
-        for (int t = 0; t < 4; t++) {
-          int64_t id = id0 + t;
-          if (!gamma_bitmap_test(bitmap, (uint64_t)id)) {
-            float dist = l2 ? fmaf(-2.0f, dv[t], qn + bv[t]) : dv[t];
-            sel.push(gamma_make_key<IP>(dist, (uint32_t)id));
-          }
-        }
-      }
-      sel.maybe_flush(64 * 4);
+  if (prime && sel.thresh == GAMMA_KEY_EMPTY &&
+      ncols <= GAMMA_SELECT_PRIME_MAX_COLS) { /* wave-uniform */
+    uint64_t m[4] = {GAMMA_KEY_EMPTY, GAMMA_KEY_EMPTY, GAMMA_KEY_EMPTY,
+                     GAMMA_KEY_EMPTY};
+    gamma_walk_row<IP>(
+        row, ncols, col_base, lane, qn, bnorms, l2, bitmap,
+        [&](uint64_t key, int slot) { m[slot] = min(m[slot], key); },
+        [](int) {});
+    uint64_t tau;
+    if (k2 <= 32) {
+      m[0] = min(min(m[0], m[1]), min(m[2], m[3]));
+      tau = gamma_wave_kth_key<1>(m, k2);
+    } else if (k2 <= 64) {
+      m[0] = min(m[0], m[2]);
+      m[1] = min(m[1], m[3]);
+      tau = gamma_wave_kth_key<2>(m, k2);
+    } else {
+      tau = gamma_wave_kth_key<4>(m, k2);
     }
-  } else {
-    for (int64_t c0 = 0; c0 < ncols; c0 += 64) {
-      int64_t c = c0 + lane;
-      if (c < ncols) {
-        int64_t id = col_base + c;
-        if (!gamma_bitmap_test(bitmap, (uint64_t)id)) {
-          float dot = row[c];
-          float dist = l2 ? fmaf(-2.0f, dot, qn + bnorms[id]) : dot;
-          sel.push(gamma_make_key<IP>(dist, (uint32_t)id));
-        }
-      }
-      sel.maybe_flush(64);
-    }
+    sel.prime(tau);
   }
+  int npush = 0, nflush = 0;
+  gamma_walk_row<IP>(
+      row, ncols, col_base, lane, qn, bnorms, l2, bitmap,
+      [&](uint64_t key, int) {
+        if (COUNT && key < sel.thresh) npush++;
+        sel.push(key);
+      },
+      [&](int margin) {
+        if (COUNT) {
+          __builtin_amdgcn_wave_barrier();
+          if (*sel.cnt > sel.cap - margin) nflush++;
+        }
+        sel.maybe_flush(margin);
+      });
   sel.finish();
   for (int i = lane; i < k2; i += 64)
     state_keys[(int64_t)q * k2 + i] = sel.buf[i];
+  if (COUNT) {
+    if (npush) atomicAdd(&stats[2 * q], npush);
+    if (lane == 0) stats[2 * q + 1] = nflush;
+  }
 }
 
 template <bool IP>
@@ -437,10 +530,28 @@ k_select_from_dots_wave(int nq, int64_t ncols, int64_t col_base,
                         const float *__restrict__ qnorms,
                         const float *__restrict__ bnorms, int l2,
                         const uint32_t *__restrict__ bitmap, int k2,
-                        uint64_t *__restrict__ state_keys, int seeded) {
+                        uint64_t *__restrict__ state_keys, int seeded,
+                        int prime) {
   extern __shared__ char smem[];
-  gamma_select_wave<IP>(smem, nq, ncols, col_base, ld, dots, qnorms, bnorms,
-                        l2, bitmap, k2, state_keys, seeded);
+  gamma_select_wave<IP, false>(smem, nq, ncols, col_base, ld, dots, qnorms,
+                               bnorms, l2, bitmap, k2, state_keys, seeded,
+                               prime, nullptr);
+}
+
+/* the same select with the walk's counters (kernel test hook only) */
+template <bool IP>
+__global__ void __launch_bounds__(512)
+k_select_from_dots_wave_stats(int nq, int64_t ncols, int64_t col_base,
+                              int64_t ld, const float *__restrict__ dots,
+                              const float *__restrict__ qnorms,
+                              const float *__restrict__ bnorms, int l2,
+                              const uint32_t *__restrict__ bitmap, int k2,
+                              uint64_t *__restrict__ state_keys, int seeded,
+                              int prime, int *__restrict__ stats) {
+  extern __shared__ char smem[];
+  gamma_select_wave<IP, true>(smem, nq, ncols, col_base, ld, dots, qnorms,
+                              bnorms, l2, bitmap, k2, state_keys, seeded,
+                              prime, stats);
 }
 
 /* the same select behind a device-side switch (see k_dots_mfma_tiled_if) */
@@ -452,11 +563,12 @@ k_select_from_dots_wave_if(int nq, int64_t ncols, int64_t col_base,
                            const float *__restrict__ bnorms, int l2,
                            const uint32_t *__restrict__ bitmap, int k2,
                            uint64_t *__restrict__ state_keys, int seeded,
-                           const int *__restrict__ run_if) {
+                           int prime, const int *__restrict__ run_if) {
   extern __shared__ char smem[];
   if (*run_if == 0) return;
-  gamma_select_wave<IP>(smem, nq, ncols, col_base, ld, dots, qnorms, bnorms,
-                        l2, bitmap, k2, state_keys, seeded);
+  gamma_select_wave<IP, false>(smem, nq, ncols, col_base, ld, dots, qnorms,
+                               bnorms, l2, bitmap, k2, state_keys, seeded,
+                               prime, nullptr);
 }
 
 /* Coarse assign, final select (gk::coarse_select phase 3): wave per query
@@ -507,13 +619,20 @@ k_coarse_final_select(int nq, int k2, int cap,
     state_keys[(int64_t)q * k2 + i] = sel.buf[i];
 }
 
+/* GAMMA_SELECT_PRIME=0 keeps the wave select's unprimed single walk (A/B
+ * runs of one build, and tests that compare the two); read per call */
+static bool gamma_select_prime() {
+  const char *e = getenv("GAMMA_SELECT_PRIME");
+  return !(e && e[0] == '0' && e[1] == 0);
+}
+
 hipError_t gk::select_from_dots(hipStream_t s, int nq, int64_t ncols,
                                 int64_t col_base, int64_t ld,
                                 const float *dots, const float *qnorms,
                                 const float *bnorms, bool l2, bool ip_order,
                                 const uint32_t *bitmap, int k2,
                                 uint64_t *state_keys, bool seeded,
-                                const int *run_if) {
+                                const int *run_if, int *wave_stats) {
   /* k2 <= 192: seeds (k2 keys) plus one 64-push interval must fit the
    * wave cap (GAMMA_WSEL_CAP - k2), with slack; covers every coarse
    * assign (nprobe). Larger k2 (FLAT top-k accumulation) -> block path. */
@@ -521,27 +640,41 @@ hipError_t gk::select_from_dots(hipStream_t s, int nq, int64_t ncols,
     const int nw = 512 / 64;
     size_t smem = (size_t)nw * GAMMA_WSEL_CAP * 8 + nw * sizeof(int);
     dim3 g((uint32_t)((nq + nw - 1) / nw));
+    const int prime = gamma_select_prime() ? 1 : 0;
+    if (wave_stats) {
+      if (run_if) return hipErrorInvalidValue;
+      if (ip_order)
+        k_select_from_dots_wave_stats<true><<<g, dim3(512), smem, s>>>(
+            nq, ncols, col_base, ld, dots, qnorms, bnorms, l2 ? 1 : 0,
+            bitmap, k2, state_keys, seeded ? 1 : 0, prime, wave_stats);
+      else
+        k_select_from_dots_wave_stats<false><<<g, dim3(512), smem, s>>>(
+            nq, ncols, col_base, ld, dots, qnorms, bnorms, l2 ? 1 : 0,
+            bitmap, k2, state_keys, seeded ? 1 : 0, prime, wave_stats);
+      return hipGetLastError();
+    }
     if (run_if) {
       if (ip_order)
         k_select_from_dots_wave_if<true><<<g, dim3(512), smem, s>>>(
             nq, ncols, col_base, ld, dots, qnorms, bnorms, l2 ? 1 : 0,
-            bitmap, k2, state_keys, seeded ? 1 : 0, run_if);
+            bitmap, k2, state_keys, seeded ? 1 : 0, prime, run_if);
       else
         k_select_from_dots_wave_if<false><<<g, dim3(512), smem, s>>>(
             nq, ncols, col_base, ld, dots, qnorms, bnorms, l2 ? 1 : 0,
-            bitmap, k2, state_keys, seeded ? 1 : 0, run_if);
+            bitmap, k2, state_keys, seeded ? 1 : 0, prime, run_if);
       return hipGetLastError();
     }
     if (ip_order)
       k_select_from_dots_wave<true><<<g, dim3(512), smem, s>>>(
           nq, ncols, col_base, ld, dots, qnorms, bnorms, l2 ? 1 : 0,
-          bitmap, k2, state_keys, seeded ? 1 : 0);
+          bitmap, k2, state_keys, seeded ? 1 : 0, prime);
     else
       k_select_from_dots_wave<false><<<g, dim3(512), smem, s>>>(
           nq, ncols, col_base, ld, dots, qnorms, bnorms, l2 ? 1 : 0,
-          bitmap, k2, state_keys, seeded ? 1 : 0);
+          bitmap, k2, state_keys, seeded ? 1 : 0, prime);
     return hipGetLastError();
   }
+  if (wave_stats) return hipErrorInvalidValue; /* wave kernel only */
   if (run_if) return hipErrorInvalidValue; /* wave kernel only */
   size_t smem = (GAMMA_SORT_CAP + k2) * 8 + 4 * sizeof(int);
   if (ip_order)

@@ -34,6 +34,18 @@ int GammaKTestSelectFromDots(int nq, int64_t ncols, int64_t col_base,
                                       bitmap, k2, state_keys, seeded != 0));
 }
 
+int GammaKTestSelectWaveStats(int nq, int64_t ncols, int64_t col_base,
+                              int64_t ld, const float *dots,
+                              const float *qnorms, const float *bnorms,
+                              int l2, int ip_order, const uint32_t *bitmap,
+                              int k2, uint64_t *state_keys, int seeded,
+                              int *stats) {
+  return kt_done(gk::select_from_dots(nullptr, nq, ncols, col_base, ld, dots,
+                                      qnorms, bnorms, l2 != 0, ip_order != 0,
+                                      bitmap, k2, state_keys, seeded != 0,
+                                      nullptr, stats));
+}
+
 int GammaKTestSelectRowsFull(int nq, int ncols, int64_t ld,
                              const float *dots, const float *qnorms,
                              const float *bnorms, int l2, int ip_order,

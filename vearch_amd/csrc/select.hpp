@@ -193,6 +193,16 @@ struct GammaWaveSelector {
     __builtin_amdgcn_wave_barrier();
   }
 
+  /* Admit only keys <= tau from here on. The caller guarantees that at
+   * least k of the keys it is about to push are <= tau, so the k-th
+   * smallest is among the admitted. Only ever tightens (a seeded
+   * selector keeps its own threshold where that is lower), so push /
+   * maybe_flush / finish keep their invariants. tau = EMPTY: no bound
+   * (and tau + 1 would wrap). */
+  __device__ __forceinline__ void prime(uint64_t tau) {
+    if (tau != GAMMA_KEY_EMPTY && tau + 1 < thresh) thresh = tau + 1;
+  }
+
   __device__ __forceinline__ void push(uint64_t key) {
     if (key < thresh) {
       int idx = atomicAdd(cnt, 1);
@@ -237,6 +247,45 @@ struct GammaWaveSelector {
     }
     if (lane == 0) *cnt = 0;
     __builtin_amdgcn_wave_barrier();
-    thresh = buf[k - 1];
+    /* min: a flush with fewer than k keys so far (buf[k-1] still EMPTY)
+     * must not lift a primed threshold; unprimed, buf[k-1] never rises */
+    thresh = min(thresh, buf[k - 1]);
   }
 };
+
+__device__ __forceinline__ uint64_t gamma_readlane_u64(uint64_t v, int j) {
+  uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, j);
+  uint32_t hi =
+      (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), j);
+  return ((uint64_t)hi << 32) | lo;
+}
+
+/* The kth smallest (kth >= 1) of the 64 * R keys the lanes of a wave hold
+ * in m[0..R): each lane ranks its own keys against every lane's (a
+ * readlane loop, 64 * R * R compares per lane: no LDS, no sort) and the
+ * holder of rank kth - 1 broadcasts. Real keys are distinct (ids are), so
+ * that holder is unique; EMPTY entries tie with each other above every
+ * real key, and when fewer than kth keys are real the answer is EMPTY.
+ * All 64 lanes must call this together. */
+template <int R>
+__device__ __forceinline__ uint64_t gamma_wave_kth_key(const uint64_t (&m)[4],
+                                                       int kth) {
+  int rank[R];
+#pragma unroll
+  for (int s = 0; s < R; s++) rank[s] = 0;
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    for (int j = 0; j < 64; j++) {
+      const uint64_t o = gamma_readlane_u64(m[r], j);
+#pragma unroll
+      for (int s = 0; s < R; s++) rank[s] += (o < m[s]) ? 1 : 0;
+    }
+  }
+  uint64_t mine = GAMMA_KEY_EMPTY;
+#pragma unroll
+  for (int s = 0; s < R; s++)
+    if (rank[s] == kth - 1) mine = m[s];
+  const uint64_t has = __ballot(mine != GAMMA_KEY_EMPTY);
+  if (has == 0) return GAMMA_KEY_EMPTY;
+  return gamma_readlane_u64(mine, __builtin_ctzll(has));
+}

@@ -32,6 +32,8 @@ def _lib():
         L.GammaKTestDotsMfma.argtypes = [vp, i32, vp, i64, i32, vp]
         L.GammaKTestSelectFromDots.argtypes = [
             i32, i64, i64, i64, vp, vp, vp, i32, i32, vp, i32, vp, i32]
+        L.GammaKTestSelectWaveStats.argtypes = [
+            i32, i64, i64, i64, vp, vp, vp, i32, i32, vp, i32, vp, i32, vp]
         L.GammaKTestSelectRowsFull.argtypes = [
             i32, i32, i64, vp, vp, vp, i32, i32, i32, vp, vp]
         L.GammaKTestArgminRows.argtypes = [i64, i32, vp, vp, vp, i32, vp]
@@ -178,6 +180,34 @@ def select_from_dots(dots, ncols, k2, l2, ip_order, qnorms=None,
           _p(bitmap, torch.int32), k2, _p(state, torch.int64),
           int(bool(seeded)))
     return state
+
+
+def select_wave_stats(dots, ncols, k2, l2, ip_order, qnorms=None,
+                      bnorms=None, col_base=0, bitmap=None, state=None,
+                      seeded=False):
+    """select_from_dots through the wave kernel's counting variant
+    (k2 <= 192). Returns (state, pushed, flushes): per query, the keys the
+    walk admitted to the selector's append region and the flushes it ran
+    before the closing one, as int32 numpy arrays of nq."""
+    assert dots.dim() == 2 and dots.stride(1) == 1
+    nq, ld = dots.shape[0], dots.stride(0)
+    assert 0 < ncols <= dots.shape[1] and 1 <= k2 <= 192
+    if l2:
+        assert qnorms is not None and bnorms is not None
+        assert qnorms.numel() >= nq and bnorms.numel() >= col_base + ncols
+    if state is None:
+        assert not seeded
+        state = torch.full((nq, k2), 0x5A5A5A5A5A5A5A5A, dtype=torch.int64,
+                           device=dots.device)
+    assert state.shape == (nq, k2) and state.is_contiguous()
+    stats = torch.zeros((nq, 2), dtype=torch.int32, device=dots.device)
+    _call("GammaKTestSelectWaveStats", nq, ncols, col_base, ld,
+          _p(dots, torch.float32), _p(qnorms, torch.float32),
+          _p(bnorms, torch.float32), int(bool(l2)), int(bool(ip_order)),
+          _p(bitmap, torch.int32), k2, _p(state, torch.int64),
+          int(bool(seeded)), _p(stats, torch.int32))
+    st = stats.cpu().numpy()
+    return state, st[:, 0].copy(), st[:, 1].copy()
 
 
 def select_rows_full(dots, ncols, k2, l2, ip_order, qnorms=None,
