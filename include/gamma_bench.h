@@ -319,6 +319,14 @@ int GammaKTestCoarseSelect(const float *Q, int nq, const float *B,
                            uint64_t *sel_keys);
 int GammaKTestCoarseCanFilter(int nq, int64_t nlist, int d, int nprobe,
                               int n1, int *knobs2);
+/* deep top-k (1024 < k2 <= 8192): gk::select_deep over S regions of k2
+ * keys per query at `stride` keys apart -> out nq x kout, sorted;
+ * gk::deep_selector_probe pushes keys[0, n) through one GammaDeepSelector
+ * whose region is 4 * k2 keys */
+int GammaKTestSelectDeep(int nq, int S, int k2, int64_t stride, int kout,
+                         const uint64_t *keys, uint64_t *out);
+int GammaKTestDeepSelectorProbe(int n, int k2, const uint64_t *keys,
+                                uint64_t *region);
 
 #ifdef __cplusplus
 }

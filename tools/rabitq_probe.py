@@ -14,7 +14,10 @@ the same nlist and nprobe, plus a FLAT table for the exact ground truth:
 
 Timed steps alternate between the tables (medians after warm-up), once with
 recall_num = 0 (the scan selects k keys, no re-rank) and once with
-recall_num = 100 (the scan selects 100 keys, the exact re-rank leg follows).
+recall_num = 100 (the scan selects 100 keys, the exact re-rank leg follows);
+--recall-num takes other values in its place, several in one run, e.g.
+1024,2048,8192 to time the deep top-k path (IVFRABITQ only: the IVFPQ table
+sits out the values beyond 1024) next to the 1024 one.
 Recorded per table and recall_num: the stage times (coarse "assign", scan,
 "post" = re-rank + final sort), recall@k against the FLAT table on the
 first --gt-nq queries, and for the scan its effective byte rate = scanned
@@ -37,7 +40,6 @@ from vearch_amd import GammaEngine  # noqa: E402
 from vearch_amd.engine import lib  # noqa: E402
 
 STAGES = ["h2d_us", "assign_us", "scan_us", "post_us", "d2h_us", "total_us"]
-RECALL_NUMS = (0, 100)
 
 
 def log(msg):
@@ -82,8 +84,15 @@ def main():
     ap.add_argument("--nb-bits", default="1",
                     help="comma-separated IVFRABITQ code widths (1, 4, 8): "
                          "one table each, all timed in the same run")
+    ap.add_argument("--recall-num", default="100",
+                    help="comma-separated recall_num values timed next to "
+                         "recall_num = 0 (up to 8192; beyond 1024 IVFRABITQ "
+                         "only)")
     ap.add_argument("--out", default="profiles/rabitq_probe.json")
     args = ap.parse_args()
+    recall_nums = (0,) + tuple(int(r) for r in args.recall_num.split(","))
+    if any(not 0 < r <= 8192 for r in recall_nums[1:]):
+        ap.error("--recall-num takes values in 1..8192")
     widths = [int(b) for b in args.nb_bits.split(",")]
     if not widths or any(b not in (1, 4, 8) for b in widths):
         ap.error("--nb-bits takes 1, 4 and 8")
@@ -132,10 +141,13 @@ def main():
             t["_eng"], q, args.nlist, args.nprobe), 1)
         t["_nq"] = t["_eng"].cache_queries(q)
         t["_runs"] = {rn: {"stages": {s: [] for s in STAGES}, "ms": []}
-                      for rn in RECALL_NUMS}
+                      for rn in recall_nums
+                      if rn <= 1024 or t["table"].startswith("IVFRABITQ")}
     for step in range(args.warmup + args.steps):
-        for rn in RECALL_NUMS:
+        for rn in recall_nums:
             for t in tables:  # alternate the tables
+                if rn not in t["_runs"]:
+                    continue
                 t0 = time.perf_counter()
                 t["_eng"].search_cached(t["_nq"], args.k, nprobe=args.nprobe,
                                         rerank=rn)
@@ -148,8 +160,7 @@ def main():
                         run["stages"][s].append(lt[s])
     for t in tables:
         t["runs"] = []
-        for rn in RECALL_NUMS:
-            run = t["_runs"][rn]
+        for rn, run in t["_runs"].items():
             r = {"recall_num": rn}
             for s in STAGES:
                 r[s.replace("_us", "_ms")] = round(
@@ -174,9 +185,14 @@ def main():
         print(json.dumps(t), flush=True)
 
     rb, pq = tables[0], tables[-1]
-    ratios = {str(rn): round(a["scan_gbytes_per_s"] / b["scan_gbytes_per_s"],
-                             4)
-              for rn, a, b in zip(RECALL_NUMS, rb["runs"], pq["runs"])}
+
+    def ratio(key, ta, tb):  # per recall_num that both tables ran
+        rb_ = {r["recall_num"]: r for r in tb["runs"]}
+        return {str(r["recall_num"]): round(
+                    r[key] / rb_[r["recall_num"]][key], 4)
+                for r in ta["runs"] if r["recall_num"] in rb_}
+
+    ratios = ratio("scan_gbytes_per_s", rb, pq)
     doc = {
         "db_size": n, "d": d, "nlist": args.nlist, "nq": args.nq,
         "gt_nq": gt_nq, "nprobe": args.nprobe, "k": args.k,
@@ -186,17 +202,12 @@ def main():
                 "FLAT table over the same vectors",
         "results": tables,
         "byte_rate_ratio_rabitq_over_ivfpq8": ratios,
-        "entry_rate_ratio_rabitq_over_ivfpq8": {
-            str(rn): round(a["scan_gentries_per_s"]
-                           / b["scan_gentries_per_s"], 4)
-            for rn, a, b in zip(RECALL_NUMS, rb["runs"], pq["runs"])},
+        "entry_rate_ratio_rabitq_over_ivfpq8":
+            ratio("scan_gentries_per_s", rb, pq),
     }
     if len(widths) > 1:  # the wider codes against the first width given
         doc["byte_rate_ratio_over_nb_bits_%d" % widths[0]] = {
-            t["table"]: {str(rn): round(a["scan_gbytes_per_s"]
-                                        / b["scan_gbytes_per_s"], 4)
-                         for rn, a, b in zip(RECALL_NUMS, t["runs"],
-                                             rb["runs"])}
+            t["table"]: ratio("scan_gbytes_per_s", t, rb)
             for t in tables[1:-1]}
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:

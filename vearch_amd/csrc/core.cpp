@@ -1455,6 +1455,14 @@ int IVFIndex::probe_split(int nq, int k2, int nprobe) const {
    * keeps the merge a single row sort) */
   if (!coded() && !binary()) return 1;
   const char *force = getenv("GAMMA_SCAN_S"); /* perf experiments */
+  if (k2 > 1024) {
+    /* deep top-k: gk::select_deep merges any S; a split costs a region of
+     * 32 k2 bytes, so stop at 8 */
+    int S = 1;
+    if (force && atoi(force) > 0) return std::min(atoi(force), 8);
+    while (nq * S < 512 && 2 * S <= nprobe && 2 * S <= 8) S *= 2;
+    return S;
+  }
   if (force && atoi(force) > 0) {
     int S = atoi(force);
     while ((int64_t)S * k2 > 2048 && S > 1) S /= 2;
@@ -1474,7 +1482,7 @@ int IVFIndex::search(const float *q_dev, int nq, int k2, int nprobe,
                      const int *kill_flag_dev, const GammaScanRerank *rr,
                      bool *fused) {
   if (fused) *fused = false;
-  if (!trained_) return -1;
+  if (!trained_ || !serves_k2(k2)) return -1;
   nprobe = std::min(nprobe, nlist_);
   if (nprobe > 1024) nprobe = 1024; /* selector cap (select.hpp) */
   if (sc.probes.reserve((size_t)nq * nprobe * 8)) return -1;
@@ -1600,11 +1608,34 @@ int IVFIndex::search(const float *q_dev, int nq, int k2, int nprobe,
     /* the factor A in the entries was encoded for the table's metric; a
      * request that overrides the metric is served as IVFPQ serves it, in
      * the requested key order over the codes as they are */
-    GAMMA_CHECK(gk::rabitq_scan(
-        s, params_.nb_bits, nq, S, d_, nprobe, k2, q_dev,
-        centroids_.as<float>(), dev_buckets_.as<GammaBucketDev>(), nlist_,
-        sc.probes.as<int64_t>(), bitmap_dev, metric_ip, out_keys_dev,
-        kill_flag_dev));
+    if (k2 <= 1024) {
+      GAMMA_CHECK(gk::rabitq_scan(
+          s, params_.nb_bits, nq, S, d_, nprobe, k2, q_dev,
+          centroids_.as<float>(), dev_buckets_.as<GammaBucketDev>(), nlist_,
+          sc.probes.as<int64_t>(), bitmap_dev, metric_ip, out_keys_dev,
+          kill_flag_dev));
+    } else {
+      /* deep top-k: the scan leaves each workgroup's k2 keys in its region
+       * of 4 k2; select_deep merges the S regions of a query into the
+       * sorted row of out_keys. Groups of queries keep the regions within
+       * kDeepRegionCapBytes; a group is a row range of every array. */
+      const size_t reg_q = (size_t)S * 4 * k2 * 8;
+      const int gq = (int)std::min<size_t>(
+          nq, std::max<size_t>(1, kDeepRegionCapBytes / reg_q));
+      if (sc.deep_regions.reserve((size_t)gq * reg_q)) return -1;
+      for (int g0 = 0; g0 < nq; g0 += gq) {
+        const int gn = std::min(gq, nq - g0);
+        GAMMA_CHECK(gk::rabitq_scan(
+            s, params_.nb_bits, gn, S, d_, nprobe, k2,
+            q_dev + (size_t)g0 * d_, centroids_.as<float>(),
+            dev_buckets_.as<GammaBucketDev>(), nlist_,
+            sc.probes.as<int64_t>() + (size_t)g0 * nprobe, bitmap_dev,
+            metric_ip, sc.deep_regions.as<uint64_t>(), kill_flag_dev));
+        GAMMA_CHECK(gk::select_deep(s, gn, S, k2, (int64_t)4 * k2, k2,
+                                    sc.deep_regions.as<uint64_t>(),
+                                    out_keys_dev + (size_t)g0 * k2));
+      }
+    }
   } else if (binary()) {
     GAMMA_CHECK(gk::binivf_scan(s, nq, S, d_, nprobe, k2,
                                 (const uint32_t *)q_dev,

@@ -256,6 +256,9 @@ struct SearchScratch {
   DeviceBuf qcol, qmap;
   std::vector<int32_t> qcol_h, qmap_h;
   DeviceBuf rot_q, rot_norms; /* OPQ-rotated queries + their norms */
+  /* deep top-k (k2 > 1024): the selectors' regions of one query group, and
+   * the sorted keys of the final gk::select_deep */
+  DeviceBuf deep_regions, deep_keys;
   bool in_use = false;
   ~SearchScratch() {
     if (stream) (void)hipStreamDestroy(stream);
@@ -287,6 +290,17 @@ class IVFIndex {
    * nsubvector KB per query at 8 bits); search() walks larger batches in
    * query groups (DESIGN.md "Wide PQ") */
   static constexpr size_t kScanTableCapBytes = (size_t)512 << 20;
+  /* deep top-k (IVFRABITQ, 1024 < k2 <= kDeepMaxK): a scan workgroup owns a
+   * region of 4 k2 keys (32 k2 bytes); search() walks batches whose regions
+   * exceed this in query groups (DESIGN.md "Deep top-k") */
+  static constexpr size_t kDeepRegionCapBytes = (size_t)256 << 20;
+  static constexpr int kDeepMaxK = 8192;
+  /* whether search() serves this k2: every kind up to 1024, IVFRABITQ up to
+   * kDeepMaxK. Beyond 1024 search() merges the probe splits itself and
+   * out_keys is nq x k2, sorted. */
+  bool serves_k2(int k2) const {
+    return k2 <= 1024 || (rabitq() && k2 <= kDeepMaxK);
+  }
   /* BINARYIVF: nlist x d/8 bytes of binarised centroids */
   int copy_binary_centroids(uint8_t *out, hipStream_t s) const;
   int train(const float *xt, int64_t n, hipStream_t s, std::string *err);

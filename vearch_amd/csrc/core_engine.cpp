@@ -849,10 +849,16 @@ int Engine::search(int nq, const float *xq, int k, int nprobe,
    * (search_preassigned, ivfpq.cc:765-776) */
   int k2 = std::max(k, recall_num);
   bool rerank = recall_num > 0;
-  if (k2 > 1024) {
+  bool use_flat = brute_force || params_.kind == IndexKind::FLAT ||
+                  !index_ || !index_->trained();
+  /* a trained IVFRABITQ table is served up to 8192 (deep top-k); every
+   * other index kind and the brute-force scan stop at 1024 */
+  const bool deep = k2 > 1024 && !use_flat && index_->serves_k2(k2);
+  if (k2 > 1024 && !deep) {
     if (filter_err)
       *filter_err = "topN+offset (or recall_num) = " + std::to_string(k2) +
-                    " exceeds this engine's supported maximum of 1024";
+                    " exceeds this engine's supported maximum of " +
+                    (!use_flat && index_->rabitq() ? "8192" : "1024");
     return -3;
   }
 
@@ -888,8 +894,6 @@ int Engine::search(int nq, const float *xq, int k, int nprobe,
       return -3;
   }
 
-  bool use_flat = brute_force || params_.kind == IndexKind::FLAT ||
-                  !index_ || !index_->trained();
   double t_assign = 0, t_scan = 0;
   bool need_canonical_rerank = true; /* FLAT & IVFFLAT canonicalize */
   bool fused = false; /* re-rank + top-k done inside the scan kernel */
@@ -921,7 +925,7 @@ int Engine::search(int nq, const float *xq, int k, int nprobe,
     if (nprobe <= 0) nprobe = index_->params().nprobe;
     if (nprobe <= 0) nprobe = 80;
     int S = index_->probe_split(nq, k2, nprobe);
-    if (S > 1 && sc.keys.reserve((size_t)nq * S * k2 * 8)) return -1;
+    if (S > 1 && !deep && sc.keys.reserve((size_t)nq * S * k2 * 8)) return -1;
     /* arm the in-flight kill flag so SetKillStatus stops the scan
      * between lists (request_context.h:83 semantics) */
     const int *kf = nullptr;
@@ -949,7 +953,9 @@ int Engine::search(int nq, const float *xq, int k, int nprobe,
                                 rerank && !bin ? &rr : nullptr, &fused);
     if (kf) KillRegistry::inst().disarm(sc.kill_flag.as<int>());
     if (rc_idx) return -1;
-    k2 = k2 * S; /* sub-block partials merge in the sort below */
+    /* sub-block partials merge in the sort below; a deep search has
+     * merged them already (sc.keys is nq x k2, sorted) */
+    if (!deep) k2 = k2 * S;
     /* ADC distances already match the oracle bit-for-bit; canonical
      * re-rank only when the caller asked for the exact rerank leg */
     /* (sub-block partials are unsorted relative to each other, but
@@ -960,7 +966,26 @@ int Engine::search(int nq, const float *xq, int k, int nprobe,
   tm.rec(2);
   if (KillRegistry::inst().killed(request_id, pid)) return -2;
 
-  if (!fused) {
+  if (deep) {
+    /* gk::rerank tiles any ncand; its keys go to gk::select_deep for the
+     * final top-k, sort_rows' LDS row being sized for 2048. Without the
+     * re-rank leg k == k2 and the merged row is the result. */
+    const uint64_t *fin = sc.keys.as<uint64_t>();
+    if (need_canonical_rerank) {
+      if (sc.deep_keys.reserve((size_t)nq * k * 8)) return -1;
+      GAMMA_CHECK(gk::rerank(s, nq, k2, dim_, qptr, raw_.dev_seg_table(),
+                             raw_.num_segs(), RawStore::SEG_SHIFT, ip,
+                             sc.keys.as<uint64_t>(),
+                             sc.keys.as<uint64_t>()));
+      GAMMA_CHECK(gk::select_deep(s, nq, 1, k2, k2, k,
+                                  sc.keys.as<uint64_t>(),
+                                  sc.deep_keys.as<uint64_t>()));
+      fin = sc.deep_keys.as<uint64_t>();
+    }
+    GAMMA_CHECK(gk::unpack_keys(s, (int64_t)nq * k, fin, ip,
+                                sc.out_d.as<float>(),
+                                sc.out_i.as<int64_t>()));
+  } else if (!fused) {
     if (need_canonical_rerank) {
       GAMMA_CHECK(gk::rerank(s, nq, k2, dim_, qptr, raw_.dev_seg_table(),
                              raw_.num_segs(), RawStore::SEG_SHIFT, ip,

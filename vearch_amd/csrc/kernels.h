@@ -320,6 +320,23 @@ hipError_t sort_rows(hipStream_t s, int nq, int ncand, int k,
                      const uint64_t *keys, bool ip, float *out_dists,
                      int64_t *out_ids);
 
+/* Deep top-k (select.hpp GammaDeepSelector, DESIGN.md "Deep top-k"): the
+ * kout smallest of the keys of each query's S regions, sorted ascending,
+ * GAMMA_KEY_EMPTY last. Region r of query q is keys[(q * S + r) * stride
+ * .. + k2), unsorted, EMPTY where it holds fewer than k2 keys; real keys
+ * are distinct. out is nq x kout and must not overlap keys. One workgroup
+ * per query: radix select, then a bitonic sort of the survivors in LDS.
+ * stride >= k2, kout <= k2, kout <= 8192. Merges the partial rows of a
+ * deep scan (stride = 4 * k2, the selector's region) and serves as the
+ * final top-k behind gk::rerank where ncand > 1024 (S = 1, stride = k2). */
+hipError_t select_deep(hipStream_t s, int nq, int S, int k2, int64_t stride,
+                       int kout, const uint64_t *keys, uint64_t *out);
+/* TEST HOOK: keys[0, n) pushed through GammaDeepSelector by one workgroup;
+ * region (4 * k2 keys) holds the k2 smallest, unsorted, EMPTY-padded, in
+ * its first k2 slots. 1024 < k2 <= 8192. */
+hipError_t deep_selector_probe(hipStream_t s, int n, int k2,
+                               const uint64_t *keys, uint64_t *region);
+
 /* unpack keys -> (dists, ids) without sorting (keys already sorted). */
 hipError_t unpack_keys(hipStream_t s, int64_t n, const uint64_t *keys,
                        bool ip, float *out_dists, int64_t *out_ids);
@@ -403,8 +420,13 @@ hipError_t rabitq_sval_buckets(hipStream_t s, int nb_bits, int nlist, int d,
  * (optional) stops the scan. Keys are gamma_make_key<ip> of the estimate
  * (L2 ascending / inner product descending, ties by id). The kernel builds
  * its query table (nb_bits 1) and the per-probe scalars itself from
- * queries and centroids. k2 <= 1024. Reads GAMMA_SCAN_BS; scores do not
- * depend on it or on S. */
+ * queries and centroids. Reads GAMMA_SCAN_BS; scores do not depend on it
+ * or on S.
+ * k2 <= 1024: out_keys is nq x S x k2, each row sorted.
+ * 1024 < k2 <= 8192: the same kernel with GammaDeepSelector; out_keys is
+ * the selectors' regions, nq x S x 4 * k2 keys, and row (q, s) holds its
+ * k2 keys unsorted, EMPTY-padded, in its first k2 slots (merge with
+ * select_deep, stride 4 * k2). Same estimates, bit for bit. */
 hipError_t rabitq_scan(hipStream_t s, int nb_bits, int nq, int S, int d,
                        int nprobe, int k2, const float *queries,
                        const float *centroids, const GammaBucketDev *buckets,

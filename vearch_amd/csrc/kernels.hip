@@ -1265,6 +1265,93 @@ hipError_t gk::sort_rows(hipStream_t s, int nq, int ncand, int k,
   return hipGetLastError();
 }
 
+/* ------------------------------------------------------------ deep select
+ * One workgroup per query: radix select (gamma_radix_kth) down to the kout
+ * smallest of the S * k2 keys of the query's S regions, straight from
+ * global memory, then the survivors (exactly min(kout, real keys)) are
+ * gathered into LDS, padded to a power of two and bitonic-sorted: at most
+ * 8192 keys = 64 KB. Gather order does not matter, the sort follows. */
+#define GAMMA_DEEP_BS 512
+
+__global__ void __launch_bounds__(GAMMA_DEEP_BS)
+k_select_deep(int nq, int S, int k2, int64_t stride, int kout, int npow2,
+              const uint64_t *keys, uint64_t *__restrict__ out) {
+  extern __shared__ char smem[];
+  uint64_t *sbuf = (uint64_t *)smem; /* npow2 */
+  GammaRadixLds *lds = (GammaRadixLds *)(sbuf + npow2);
+  const int q = blockIdx.x;
+  if (q >= nq) return;
+  const uint64_t *kq = keys + (int64_t)q * S * stride;
+  const int n = S * k2;
+  auto load = [&](int i) {
+    const int s = i / k2;
+    return kq[(int64_t)s * stride + (i - s * k2)];
+  };
+  int shift;
+  uint64_t prefix;
+  gamma_radix_kth(load, n, kout, lds, shift, prefix);
+  if (threadIdx.x == 0) lds->nkeep = 0;
+  __syncthreads();
+  const uint64_t top = prefix >> shift;
+  for (int i = threadIdx.x; i < n; i += GAMMA_DEEP_BS) {
+    const uint64_t key = load(i);
+    if (key != GAMMA_KEY_EMPTY && (key >> shift) <= top) {
+      const uint32_t at = atomicAdd(&lds->nkeep, 1u);
+      if (at < (uint32_t)npow2) sbuf[at] = key; /* always, by the select */
+    }
+  }
+  __syncthreads();
+  const int kept = min((int)lds->nkeep, npow2);
+  for (int i = kept + threadIdx.x; i < npow2; i += GAMMA_DEEP_BS)
+    sbuf[i] = GAMMA_KEY_EMPTY;
+  gamma_bitonic_sort(sbuf, npow2);
+  for (int i = threadIdx.x; i < kout; i += GAMMA_DEEP_BS)
+    out[(int64_t)q * kout + i] = sbuf[i];
+}
+
+hipError_t gk::select_deep(hipStream_t s, int nq, int S, int k2,
+                           int64_t stride, int kout, const uint64_t *keys,
+                           uint64_t *out) {
+  if (nq <= 0) return hipSuccess;
+  if (S <= 0 || k2 <= 0 || stride < k2 || kout <= 0 || kout > k2 ||
+      kout > GAMMA_DEEP_MAX_K || (int64_t)S * k2 > 0x7fffffffll)
+    return hipErrorInvalidValue;
+  int npow2 = 1;
+  while (npow2 < kout) npow2 <<= 1;
+  const size_t smem = (size_t)npow2 * 8 + sizeof(GammaRadixLds);
+  k_select_deep<<<dim3((uint32_t)nq), dim3(GAMMA_DEEP_BS), smem, s>>>(
+      nq, S, k2, stride, kout, npow2, keys, out);
+  return hipGetLastError();
+}
+
+/* TEST HOOK: one workgroup pushes keys[0, n) through GammaDeepSelector,
+ * one key per thread per step, and leaves the selector's k2 keys, unsorted,
+ * in region[0, k2). */
+__global__ void __launch_bounds__(GAMMA_DEEP_BS)
+k_deep_selector_probe(int n, int k2, const uint64_t *__restrict__ keys,
+                      uint64_t *region) {
+  __shared__ uint64_t buf[GAMMA_SORT_CAP];
+  __shared__ GammaRadixLds lds;
+  __shared__ int state[2];
+  GammaDeepSelector sel;
+  sel.init(buf, &lds, state, region, k2);
+  for (int base = 0; base < n; base += GAMMA_DEEP_BS) {
+    const int i = base + threadIdx.x;
+    if (i < n) sel.push(keys[i]);
+    sel.maybe_flush(GAMMA_DEEP_BS);
+  }
+  sel.finish();
+}
+
+hipError_t gk::deep_selector_probe(hipStream_t s, int n, int k2,
+                                   const uint64_t *keys, uint64_t *region) {
+  if (n < 0 || k2 <= 1024 || k2 > GAMMA_DEEP_MAX_K)
+    return hipErrorInvalidValue;
+  k_deep_selector_probe<<<dim3(1), dim3(GAMMA_DEEP_BS), 0, s>>>(n, k2, keys,
+                                                                region);
+  return hipGetLastError();
+}
+
 /* ----------------------------------------------------------- unpack keys */
 template <bool IP>
 __global__ void k_unpack(int64_t n, const uint64_t *__restrict__ keys,

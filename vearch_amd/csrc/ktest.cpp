@@ -308,4 +308,14 @@ int GammaKTestCoarseCanFilter(int nq, int64_t nlist, int d, int nprobe,
   return gk::coarse_can_filter(nq, nlist, d, nprobe, n1) ? 1 : 0;
 }
 
+int GammaKTestSelectDeep(int nq, int S, int k2, int64_t stride, int kout,
+                         const uint64_t *keys, uint64_t *out) {
+  return kt_done(gk::select_deep(nullptr, nq, S, k2, stride, kout, keys, out));
+}
+
+int GammaKTestDeepSelectorProbe(int n, int k2, const uint64_t *keys,
+                                uint64_t *region) {
+  return kt_done(gk::deep_selector_probe(nullptr, n, k2, keys, region));
+}
+
 } /* extern "C" */

@@ -411,15 +411,20 @@ struct GammaRbqElem {
 __host__ __device__ static size_t gamma_rbq_tab_bytes(int nb_bits, int d) {
   return nb_bits == 1 ? (size_t)d * 16 : 0;
 }
-__host__ __device__ static size_t gamma_rbq_qs_off(size_t tab, int k2) {
-  return tab + ((size_t)GAMMA_SORT_CAP + k2) * 8;
+/* deep (GammaDeepSelector): the append buffer and the radix scratch take
+ * the place of the scratch + k2 result keys */
+__host__ __device__ static size_t gamma_rbq_qs_off(size_t tab, int k2,
+                                                   bool deep = false) {
+  return tab + (deep ? (size_t)GAMMA_SORT_CAP * 8 + sizeof(GammaRadixLds)
+                     : ((size_t)GAMMA_SORT_CAP + k2) * 8);
 }
 __host__ __device__ static size_t gamma_rbq_chunk_off(size_t tab, int d,
-                                                      int k2) {
-  return (gamma_rbq_qs_off(tab, k2) + (size_t)d * 4 + 7) / 8 * 8;
+                                                      int k2,
+                                                      bool deep = false) {
+  return (gamma_rbq_qs_off(tab, k2, deep) + (size_t)d * 4 + 7) / 8 * 8;
 }
-static size_t gamma_rbq_smem(int nb_bits, int d, int k2) {
-  return gamma_rbq_chunk_off(gamma_rbq_tab_bytes(nb_bits, d), d, k2) +
+static size_t gamma_rbq_smem(int nb_bits, int d, int k2, bool deep = false) {
+  return gamma_rbq_chunk_off(gamma_rbq_tab_bytes(nb_bits, d), d, k2, deep) +
          sizeof(GammaRbqChunk);
 }
 
@@ -494,7 +499,11 @@ __device__ __forceinline__ void gamma_rbq_qc(const float *qs,
   s1 = b;
 }
 
-template <bool IP, int B, int U, int NU, int BS>
+/* SEL = GammaSelector: out_keys is nq x S x k2. SEL = GammaDeepSelector:
+ * out_keys is the selectors' regions, GAMMA_DEEP_REGION(k2) keys per (query,
+ * sub-block); the workgroup's k2 keys end up in the first k2 slots of its
+ * own. Everything between init and finish is one text. */
+template <bool IP, int B, int U, int NU, int BS, class SEL = GammaSelector>
 __global__ void __launch_bounds__(BS)
 k_rabitq_scan(int nq, int S, int d, int nprobe, int k2,
               const float *__restrict__ queries,
@@ -510,10 +519,10 @@ k_rabitq_scan(int nq, int S, int d, int nprobe, int k2,
   const size_t tab = gamma_rbq_tab_bytes(B, d);
   [[maybe_unused]] float *lut = (float *)smem; /* B == 1: d/4 x 16 */
   uint64_t *sortbuf = (uint64_t *)(smem + tab);
-  uint64_t *res = sortbuf + GAMMA_SORT_CAP;
-  float *qs = (float *)(smem + gamma_rbq_qs_off(tab, k2)); /* d */
+  constexpr bool DEEP = std::is_same<SEL, GammaDeepSelector>::value;
+  float *qs = (float *)(smem + gamma_rbq_qs_off(tab, k2, DEEP)); /* d */
   GammaRbqChunk *ch =
-      (GammaRbqChunk *)(smem + gamma_rbq_chunk_off(tab, d, k2));
+      (GammaRbqChunk *)(smem + gamma_rbq_chunk_off(tab, d, k2, DEEP));
 
   const int q = blockIdx.x / S;
   const int sub = blockIdx.x - q * S;
@@ -523,8 +532,12 @@ k_rabitq_scan(int nq, int S, int d, int nprobe, int k2,
   [[maybe_unused]] const gamma_cf32p qc = (gamma_cf32p)qg;
   for (int i = threadIdx.x; i < d; i += BS) qs[i] = qg[i];
 
-  GammaSelector sel;
-  sel.init(sortbuf, res, ch->state, k2); /* has the barrier qs needs */
+  SEL sel; /* init has the barrier qs needs */
+  if constexpr (DEEP)
+    sel.init(sortbuf, (GammaRadixLds *)(sortbuf + GAMMA_SORT_CAP), ch->state,
+             out_keys + (size_t)blockIdx.x * GAMMA_DEEP_REGION(k2), k2);
+  else
+    sel.init(sortbuf, sortbuf + GAMMA_SORT_CAP, ch->state, k2);
 
   if constexpr (B == 1) {
     for (int e = threadIdx.x; e < d * 4; e += BS) {
@@ -683,7 +696,8 @@ k_rabitq_scan(int nq, int S, int d, int nprobe, int k2,
      * k_ivfpq_scan's fast path (reasons there) */
     killed = sp.killed;
     const unsigned niter = (sp.total + BS - 1) / BS;
-    const bool flush_each = k2 + 2 * BS > GAMMA_SORT_CAP;
+    /* deep: the whole scratch is append room */
+    const bool flush_each = !DEEP && k2 + 2 * BS > GAMMA_SORT_CAP;
     const int fmargin = flush_each ? BS : 2 * BS;
     auto pass = [&](GammaRbqElem<U, NU> &nxt, const GammaRbqElem<U, NU> &cur_e,
                     unsigned it_nxt, int slot, bool check) {
@@ -713,8 +727,10 @@ k_rabitq_scan(int nq, int S, int d, int nprobe, int k2,
     sel.maybe_flush(fmargin);
   }
   sel.finish();
-  for (int i = threadIdx.x; i < k2; i += BS)
-    out_keys[((int64_t)q * S + sub) * k2 + i] = res[i];
+  if constexpr (!DEEP) {
+    for (int i = threadIdx.x; i < k2; i += BS)
+      out_keys[((int64_t)q * S + sub) * k2 + i] = sel.res[i];
+  }
 }
 
 hipError_t gk::rabitq_scan(hipStream_t s, int nb_bits, int nq, int S, int d,
@@ -726,9 +742,10 @@ hipError_t gk::rabitq_scan(hipStream_t s, int nb_bits, int nq, int S, int d,
                            const int *kill_flag) {
   if (nq <= 0) return hipSuccess;
   if (!gamma_rbq_ok(d, nb_bits) || S <= 0 || nprobe <= 0 || k2 <= 0 ||
-      k2 > 1024)
+      k2 > GAMMA_DEEP_MAX_K)
     return hipErrorInvalidValue;
-  const size_t smem = gamma_rbq_smem(nb_bits, d, k2);
+  const bool deep = k2 > 1024;
+  const size_t smem = gamma_rbq_smem(nb_bits, d, k2, deep);
   if (smem > 160 * 1024) return hipErrorInvalidValue;
   dim3 g((uint32_t)nq * (uint32_t)S);
   const int W = d * nb_bits / 32; /* code words; the entry is W + 2 */
@@ -737,11 +754,18 @@ hipError_t gk::rabitq_scan(hipStream_t s, int nb_bits, int nq, int S, int d,
       gamma_pick<256, 512>(gamma_scan_bs(), [&](auto bs) {
         auto launch = [&](auto u, auto nu) {
           constexpr int BSV = decltype(bs)::value;
-          k_rabitq_scan<decltype(ipc)::value, decltype(b)::value,
-                        decltype(u)::value, decltype(nu)::value, BSV>
-              <<<g, dim3(BSV), smem, s>>>(
-                  nq, S, d, nprobe, k2, queries, centroids, buckets, nlist,
-                  probes, bitmap, out_keys, kill_flag);
+          auto go = [&](auto kernel) {
+            kernel<<<g, dim3(BSV), smem, s>>>(
+                nq, S, d, nprobe, k2, queries, centroids, buckets, nlist,
+                probes, bitmap, out_keys, kill_flag);
+          };
+          if (deep)
+            go(k_rabitq_scan<decltype(ipc)::value, decltype(b)::value,
+                             decltype(u)::value, decltype(nu)::value, BSV,
+                             GammaDeepSelector>);
+          else
+            go(k_rabitq_scan<decltype(ipc)::value, decltype(b)::value,
+                             decltype(u)::value, decltype(nu)::value, BSV>);
         };
         /* the table of the head comment: (U, NU) by entry size */
         if constexpr (decltype(b)::value == 1) {

@@ -147,6 +147,192 @@ struct GammaSelector {
   }
 };
 
+/* ------------------------------------------------------------------------
+ * Deep top-k (1024 < k <= GAMMA_DEEP_MAX_K). k keys plus an append region
+ * of the same order do not fit LDS next to a scan's own staging, and a
+ * bitonic flush over 16 K keys is the wrong algorithm, so the running
+ * state lives in global memory and is compacted by radix select
+ * (DESIGN.md "Deep top-k").
+ *
+ * gamma_radix_kth: MSD radix select over the n keys load(0..n): 8-bit
+ * digits from the top, a 256-bin LDS histogram per pass, wave 0 scans the
+ * bins for the one that holds rank kth (1-based, among the keys that are
+ * not EMPTY). It stops as soon as that bin holds ONE key: real keys are
+ * distinct (ids are), so after at most 8 passes it does. Result: (shift,
+ * prefix) with exactly min(kth, real keys) real keys satisfying
+ *   (key >> shift) <= (prefix >> shift);
+ * the key with equality there is the kth smallest. Fewer than kth + 1 real
+ * keys: shift = 0, prefix = EMPTY - 1 (every real key). All threads call
+ * it together; barriers inside. */
+#define GAMMA_DEEP_MAX_K 8192
+#define GAMMA_DEEP_REGION(k) (4 * (size_t)(k)) /* keys per region */
+
+struct GammaRadixLds {
+  uint32_t hist[256];
+  uint32_t bin, before, count, total;
+  uint32_t wcnt[2][16]; /* per-wave keep counts of a compaction tile */
+  uint32_t nkeep, pad;
+  uint64_t pivot;
+};
+
+template <class Load>
+__device__ inline void gamma_radix_kth(Load load, int n, int kth,
+                                       GammaRadixLds *lds, int &shift,
+                                       uint64_t &prefix) {
+  const int tid = threadIdx.x, nt = blockDim.x;
+  uint32_t r = (uint32_t)kth;
+  prefix = 0;
+  for (int p = 0; p < 8; p++) {
+    const int sh = 56 - 8 * p;
+    const uint64_t himask = p ? ~0ull << (sh + 8) : 0ull;
+    for (int i = tid; i < 256; i += nt) lds->hist[i] = 0;
+    __syncthreads();
+    for (int i = tid; i < n; i += nt) {
+      const uint64_t key = load(i);
+      if (key != GAMMA_KEY_EMPTY && (key & himask) == prefix)
+        atomicAdd(&lds->hist[(uint32_t)(key >> sh) & 255u], 1u);
+    }
+    __syncthreads();
+    if (tid < 64) { /* wave 0: lane l owns bins 4l .. 4l+3 */
+      uint32_t c[4], s = 0;
+#pragma unroll
+      for (int j = 0; j < 4; j++) { c[j] = lds->hist[4 * tid + j]; s += c[j]; }
+      uint32_t incl = s;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t t = __shfl_up(incl, o, 64);
+        if (tid >= o) incl += t;
+      }
+      uint32_t excl = incl - s;
+      if (excl < r && r <= incl) { /* one lane: the bins partition the keys */
+        int b = 0;
+#pragma unroll
+        for (int j = 0; j < 3; j++)
+          if (r > excl + c[j] && b == j) { excl += c[j]; b = j + 1; }
+        lds->bin = 4 * tid + b;
+        lds->before = excl;
+        lds->count = b == 0 ? c[0] : b == 1 ? c[1] : b == 2 ? c[2] : c[3];
+      }
+      if (tid == 63) lds->total = incl;
+    }
+    __syncthreads();
+    if (lds->total < r || (p == 0 && lds->total == r)) { /* p == 0 only */
+      shift = 0;
+      prefix = GAMMA_KEY_EMPTY - 1;
+      return;
+    }
+    prefix |= (uint64_t)lds->bin << sh;
+    r -= lds->before;
+    shift = sh;
+    if (lds->count == 1) return;
+  }
+}
+
+/* GammaDeepSelector: GammaSelector's protocol (init / push / maybe_flush /
+ * finish, all threads together, exact u64 keys, a key is dropped only when
+ * it is >= the current k-th key) with its state in global memory.
+ *   buf    LDS append buffer, GAMMA_SORT_CAP keys, filled through one LDS
+ *          atomic like GammaSelector's
+ *   region GAMMA_DEEP_REGION(k) keys of global memory that only this
+ *          workgroup touches, so workgroup barriers order every access
+ *   rn     keys in the region (uniform scalar), thresh in a register
+ * flush: buf is appended to the region with coalesced stores, no sort.
+ * When the region cannot take another full buf it is compacted in place:
+ * gamma_radix_kth finds the k-th key, a ballot / prefix stream compaction
+ * keeps the k keys <= it, in tiles of one key per thread, and thresh
+ * becomes that key. The region stays unsorted. finish leaves exactly k keys
+ * in region[0, k), EMPTY behind the real ones.
+ * A tile reads its keys before the barrier and writes them behind it, at
+ * positions below the tile's own end, so the in-place move never overwrites
+ * a key that is still to be read.
+ * Invariant on entry of flush_: rn + GAMMA_SORT_CAP <= R. It holds after
+ * init (R = 4 k > 2048) and after a compaction (3 k > 2048). */
+struct GammaDeepSelector {
+  uint64_t *buf;
+  GammaRadixLds *lds;
+  int *state;
+  uint64_t *region;
+  int k, rn;
+  uint64_t thresh;
+
+  __device__ void init(uint64_t *buf_, GammaRadixLds *lds_, int *state_,
+                       uint64_t *region_, int k_) {
+    buf = buf_; lds = lds_; state = state_; region = region_; k = k_;
+    rn = 0;
+    thresh = GAMMA_KEY_EMPTY;
+    if (threadIdx.x == 0) state[0] = 0;
+    __syncthreads();
+  }
+
+  __device__ __forceinline__ void push(uint64_t key) {
+    if (key < thresh) {
+      int idx = atomicAdd(&state[0], 1);
+      buf[idx] = key; /* in range by the maybe_flush invariant */
+    }
+  }
+
+  __device__ __forceinline__ void maybe_flush(int margin) {
+    __syncthreads();
+    if (state[0] > GAMMA_SORT_CAP - margin) flush_();
+  }
+
+  __device__ void finish() {
+    __syncthreads();
+    flush_();
+    if (rn > k) compact_();
+    for (int i = rn + threadIdx.x; i < k; i += blockDim.x)
+      region[i] = GAMMA_KEY_EMPTY;
+    __syncthreads();
+  }
+
+ private:
+  __device__ void flush_() {
+    int total = state[0];
+    if (total > GAMMA_SORT_CAP) total = GAMMA_SORT_CAP; /* belt & braces */
+    total = __builtin_amdgcn_readfirstlane(total);
+    for (int i = threadIdx.x; i < total; i += blockDim.x)
+      region[rn + i] = buf[i];
+    rn += total;
+    __syncthreads();
+    if (threadIdx.x == 0) state[0] = 0;
+    if (rn + GAMMA_SORT_CAP > (int)GAMMA_DEEP_REGION(k)) compact_();
+    __syncthreads();
+  }
+
+  /* rn > k on entry; k keys and thresh = the k-th on exit */
+  __device__ void compact_() {
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int lane = tid & 63, wave = tid >> 6, nw = (nt + 63) >> 6;
+    int shift;
+    uint64_t prefix;
+    const uint64_t *rd = region;
+    gamma_radix_kth([&](int i) { return rd[i]; }, rn, k, lds, shift, prefix);
+    const uint64_t top = prefix >> shift;
+    int cnt = 0, slot = 0;
+    for (int base = 0; base < rn; base += nt, slot ^= 1) {
+      const int i = base + tid;
+      const uint64_t key = i < rn ? region[i] : GAMMA_KEY_EMPTY;
+      const bool keep = i < rn && (key >> shift) <= top;
+      if (keep && (key >> shift) == top) lds->pivot = key;
+      const uint64_t m = __ballot(keep);
+      if (lane == 0) lds->wcnt[slot][wave] = (uint32_t)__popcll(m);
+      __syncthreads();
+      int before = 0, all = 0;
+      for (int w = 0; w < nw; w++) {
+        const int c = (int)lds->wcnt[slot][w];
+        before += w < wave ? c : 0;
+        all += c;
+      }
+      if (keep)
+        region[cnt + before + __popcll(m & ((1ull << lane) - 1ull))] = key;
+      cnt += all;
+    }
+    __syncthreads();
+    rn = __builtin_amdgcn_readfirstlane(cnt);
+    thresh = lds->pivot;
+  }
+};
+
 /* delete-bitmap test (1 = deleted), u32 words; null bitmap = none */
 __device__ __forceinline__ bool gamma_bitmap_test(const uint32_t *bm,
                                                   uint64_t id) {

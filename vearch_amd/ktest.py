@@ -87,6 +87,8 @@ def _lib():
             vp, vp]
         L.GammaKTestCoarseCanFilter.argtypes = [
             i32, i64, i32, i32, i32, c.POINTER(c.c_int)]
+        L.GammaKTestSelectDeep.argtypes = [i32, i32, i32, i64, i32, vp, vp]
+        L.GammaKTestDeepSelectorProbe.argtypes = [i32, i32, vp, vp]
         _ready = True
     return L
 
@@ -265,6 +267,42 @@ def sort_rows(keys, k, ip):
     _call("GammaKTestSortRows", nq, ncand, k, _p(keys, torch.int64),
           int(bool(ip)), _p(od), _p(oi))
     return od, oi
+
+
+def select_deep(keys, kout, stride=None):
+    """gk::select_deep: keys numpy uint64 (nq, S, k2), unsorted, EMPTY where
+    a region holds fewer -> numpy uint64 (nq, kout), the kout smallest of
+    each query sorted ascending. stride > k2 places every region in a
+    stride-wide row (the slack is filled with a pattern the kernel must not
+    read)."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    nq, S, k2 = keys.shape
+    stride = k2 if stride is None else stride
+    wide = np.full((nq, S, stride), 0x1111111111111111, dtype=np.uint64)
+    wide[:, :, :k2] = keys
+    k_d = keys_to_dev(wide)
+    out = torch.full((nq, kout), 0x5A5A5A5A5A5A5A5A, dtype=torch.int64,
+                     device="cuda")
+    _call("GammaKTestSelectDeep", nq, S, k2, stride, kout,
+          _p(k_d, torch.int64), _p(out, torch.int64))
+    return keys_to_np(out)
+
+
+def deep_selector(keys, k2):
+    """keys numpy uint64 (n,), distinct, pushed in this order through one
+    GammaDeepSelector (gk::deep_selector_probe); its region, sorted by
+    gk::select_deep -> numpy uint64 (k2,), EMPTY-padded."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    k_d = keys_to_dev(keys)
+    region = torch.full((4 * k2,), 0x1111111111111111, dtype=torch.int64,
+                        device="cuda")
+    _call("GammaKTestDeepSelectorProbe", keys.shape[0], k2,
+          _p(k_d, torch.int64), _p(region, torch.int64))
+    out = torch.full((1, k2), 0x5A5A5A5A5A5A5A5A, dtype=torch.int64,
+                     device="cuda")
+    _call("GammaKTestSelectDeep", 1, 1, k2, 4 * k2, k2,
+          _p(region, torch.int64), _p(out, torch.int64))
+    return keys_to_np(out)[0]
 
 
 def coarse_can_filter(nq, nlist, d, nprobe, n1=0):
