@@ -290,7 +290,9 @@ int GammaKTestHammingFlatScan(int nq, int64_t n, int W, int k2,
  * asg_const), centroids (nlist x d) -> entries (n x code_size bytes) and
  * svals (n floats: sum_j u_j * c_j over the centroid's coordinates, u_j the
  * bit at nb_bits 1). RabitqScan has GammaKTestIvfpqScan's bucket / probe /
- * key layout with such entries and svals. */
+ * key layout with such entries and svals; for k2 > 1024 out_keys is the
+ * deep selector's regions, nq x S x 4 * k2 keys. RabitqScanIsTiled returns
+ * gk::rabitq_scan_is_tiled (1 / 0) under the current GAMMA_RBQ_TILED. */
 int GammaKTestRabitqEncode(int nb_bits, int64_t n, int d, const float *x,
                            const int32_t *asg, int asg_const, int nlist,
                            const float *centroids, int ip, uint8_t *entries,
@@ -301,6 +303,7 @@ int GammaKTestRabitqScan(int nb_bits, int nq, int S, int d, int nprobe,
                          int nlist, const int64_t *probes,
                          const uint32_t *bitmap, int ip, uint64_t *out_keys,
                          const int *kill_flag);
+int GammaKTestRabitqScanIsTiled(int nb_bits, int d);
 int GammaKTestRabitqSvalBuckets(int nb_bits, int nlist, int d,
                                 const void *bks_dev, const float *centroids);
 /* gk::coarse_select, the seed-filtered coarse assign (kernels.h): dots is

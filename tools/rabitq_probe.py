@@ -24,6 +24,12 @@ first --gt-nq queries, and for the scan its effective byte rate = scanned
 entries * bytes per entry / scan time (entries scanned per query = sum of
 the probed lists' sizes, from the engine's own probes).
 
+Every IVFRABITQ table records whether its scan takes the tiled entry
+movement (gk::rabitq_scan_is_tiled). --tiled-ab times each nb_bits 4 / 8
+table a second time, in the same alternation, with GAMMA_RBQ_TILED set
+against the default: 0 (streamed) where the default is tiled, 1 (tiled)
+where the entry is register-resident. Such runs carry "tiled_knob".
+
 Writes one JSON document to --out and echoes one JSON line per table.
 """
 import argparse
@@ -36,7 +42,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import oracle as orc  # noqa: E402
-from vearch_amd import GammaEngine  # noqa: E402
+from vearch_amd import GammaEngine, ktest  # noqa: E402
 from vearch_amd.engine import lib  # noqa: E402
 
 STAGES = ["h2d_us", "assign_us", "scan_us", "post_us", "d2h_us", "total_us"]
@@ -88,6 +94,9 @@ def main():
                     help="comma-separated recall_num values timed next to "
                          "recall_num = 0 (up to 8192; beyond 1024 IVFRABITQ "
                          "only)")
+    ap.add_argument("--tiled-ab", action="store_true",
+                    help="time the nb_bits 4 / 8 tables under the opposite "
+                         "GAMMA_RBQ_TILED too")
     ap.add_argument("--out", default="profiles/rabitq_probe.json")
     args = ap.parse_args()
     recall_nums = (0,) + tuple(int(r) for r in args.recall_num.split(","))
@@ -98,6 +107,8 @@ def main():
         ap.error("--nb-bits takes 1, 4 and 8")
     if args.steps < 5:
         ap.error("--steps must be >= 5 (medians)")
+    if "GAMMA_RBQ_TILED" in os.environ:
+        ap.error("unset GAMMA_RBQ_TILED: the probe sets it per run")
     n, d = args.db_size, args.d
     train_n = min(n, max(160_000, 39 * args.nlist))
     gt_nq = min(args.gt_nq, args.nq)
@@ -117,14 +128,14 @@ def main():
               '"training_threshold": %d, "bucket_max_size": 12800000'
               % (args.nlist, train_n))
     specs = [("IVFRABITQ nb_bits=%d L2" % b, "IVFRABITQ",
-              '{%s, "nb_bits": %d}' % (common, b), d * b // 8 + 8)
+              '{%s, "nb_bits": %d}' % (common, b), d * b // 8 + 8, b)
              for b in widths] + [
         ("IVFPQ m=%d 8-bit L2" % args.m, "IVFPQ",
          '{%s, "nsubvector": %d, "nbits_per_idx": 8}' % (common, args.m),
-         args.m),
+         args.m, 0),
     ]
     tables = []
-    for name, itype, params, code_bytes in specs:
+    for name, itype, params, code_bytes, nb in specs:
         t0 = time.time()
         wide = itype == "IVFRABITQ" and code_bytes != d // 8 + 8
         eng = build("/tmp/gamma_rbqprobe_" + itype
@@ -133,6 +144,13 @@ def main():
         tables.append({"table": name, "d": d, "code_bytes": code_bytes,
                        "scan_bytes_per_entry": 4 + code_bytes + 4,
                        "build_s": round(time.time() - t0, 1), "_eng": eng})
+        # the knobs this table is timed under: None = the environment's
+        tables[-1]["_knobs"] = [None]
+        if nb:
+            tiled = ktest.rabitq_scan_is_tiled(nb, d)
+            tables[-1]["scan_tiled"] = tiled
+            if args.tiled_ab and nb > 1:
+                tables[-1]["_knobs"].append("0" if tiled else "1")
         log(f"built {name} {tables[-1]['build_s']}s")
     del base
 
@@ -140,28 +158,40 @@ def main():
         t["scanned_entries_per_query"] = round(scanned_per_query(
             t["_eng"], q, args.nlist, args.nprobe), 1)
         t["_nq"] = t["_eng"].cache_queries(q)
-        t["_runs"] = {rn: {"stages": {s: [] for s in STAGES}, "ms": []}
-                      for rn in recall_nums
+        t["_runs"] = {(rn, kn): {"stages": {s: [] for s in STAGES}, "ms": []}
+                      for rn in recall_nums for kn in t["_knobs"]
                       if rn <= 1024 or t["table"].startswith("IVFRABITQ")}
+
+    def search(t, rn, kn, fn):  # the knob is read at every launch
+        if kn is not None:
+            os.environ["GAMMA_RBQ_TILED"] = kn
+        try:
+            return fn(rn)
+        finally:
+            os.environ.pop("GAMMA_RBQ_TILED", None)
+
     for step in range(args.warmup + args.steps):
         for rn in recall_nums:
-            for t in tables:  # alternate the tables
-                if rn not in t["_runs"]:
+            for t, kn in [(t, kn) for kn in (None, "0", "1")
+                          for t in tables]:  # alternate the tables
+                if (rn, kn) not in t["_runs"]:
                     continue
                 t0 = time.perf_counter()
-                t["_eng"].search_cached(t["_nq"], args.k, nprobe=args.nprobe,
-                                        rerank=rn)
+                search(t, rn, kn, lambda rn: t["_eng"].search_cached(
+                    t["_nq"], args.k, nprobe=args.nprobe, rerank=rn))
                 dt = time.perf_counter() - t0
                 if step >= args.warmup:
-                    run = t["_runs"][rn]
+                    run = t["_runs"][(rn, kn)]
                     run["ms"].append(dt * 1e3)
                     lt = t["_eng"].last_timing()
                     for s in STAGES:
                         run["stages"][s].append(lt[s])
     for t in tables:
         t["runs"] = []
-        for rn, run in t["_runs"].items():
+        for (rn, kn), run in t["_runs"].items():
             r = {"recall_num": rn}
+            if kn is not None:
+                r["tiled_knob"] = int(kn)
             for s in STAGES:
                 r[s.replace("_us", "_ms")] = round(
                     float(np.median(run["stages"][s])) / 1e3, 4)
@@ -175,8 +205,8 @@ def main():
                 / 1e9, 1)
             r["scan_gentries_per_s"] = round(
                 scanned / (r["scan_ms"] * 1e-3) / 1e9, 2)
-            _, ids = t["_eng"].raw_search(q[:gt_nq], args.k,
-                                          nprobe=args.nprobe, rerank=rn)
+            _, ids = search(t, rn, kn, lambda rn: t["_eng"].raw_search(
+                q[:gt_nq], args.k, nprobe=args.nprobe, rerank=rn))
             r["recall_at_k"] = round(recall_at(gt, ids, args.k), 4)
             t["runs"].append(r)
         t["_eng"].close()
@@ -187,9 +217,11 @@ def main():
     rb, pq = tables[0], tables[-1]
 
     def ratio(key, ta, tb):  # per recall_num that both tables ran
-        rb_ = {r["recall_num"]: r for r in tb["runs"]}
-        return {str(r["recall_num"]): round(
-                    r[key] / rb_[r["recall_num"]][key], 4)
+        rb_ = {r["recall_num"]: r for r in tb["runs"]
+               if "tiled_knob" not in r}
+        return {str(r["recall_num"]) + ("" if "tiled_knob" not in r else
+                                        " tiled_knob=%d" % r["tiled_knob"]):
+                round(r[key] / rb_[r["recall_num"]][key], 4)
                 for r in ta["runs"] if r["recall_num"] in rb_}
 
     ratios = ratio("scan_gbytes_per_s", rb, pq)

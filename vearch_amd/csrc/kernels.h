@@ -433,5 +433,12 @@ hipError_t rabitq_scan(hipStream_t s, int nb_bits, int nq, int S, int d,
                        int nlist, const int64_t *probes,
                        const uint32_t *bitmap, bool ip, uint64_t *out_keys,
                        const int *kill_flag);
+/* Whether rabitq_scan moves the entries of such a table through its LDS
+ * tile (rabitq_kernels.hpp, "the tiled movement") under the current
+ * GAMMA_RBQ_TILED: unset, the nb_bits 4 and 8 shapes whose entry does not
+ * fit registers (all but d = 64, 128, 256 at 4 bits and 32, 64, 128 at 8);
+ * 1, every nb_bits 4 or 8 launch; 0, none. Never at nb_bits 1. The movement
+ * does not enter the scores. */
+bool rabitq_scan_is_tiled(int nb_bits, int d);
 
 }  // namespace gk

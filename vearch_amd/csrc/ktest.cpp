@@ -280,6 +280,10 @@ int GammaKTestRabitqScan(int nb_bits, int nq, int S, int d, int nprobe,
                                  kill_flag));
 }
 
+int GammaKTestRabitqScanIsTiled(int nb_bits, int d) {
+  return gk::rabitq_scan_is_tiled(nb_bits, d) ? 1 : 0;
+}
+
 int GammaKTestRabitqSvalBuckets(int nb_bits, int nlist, int d,
                                 const void *bks_dev,
                                 const float *centroids) {

@@ -44,12 +44,15 @@
  * Who serves which (nb_bits, d), as gk::rabitq_scan dispatches, always at
  * BS = GAMMA_SCAN_BS: k_rabitq_scan<IP, B, U, NU, BS> with the entry moved
  * in units of U words. NU > 0 holds the whole entry in registers, NU = 0
- * streams it.
+ * streams it, NU = -1 tiles it through LDS (B = 4, 8 only).
  * - B = 1: d = 32, 64, 128, 256 (W = 1, 2, 4, 8) -> (U, NU) = (1, 3),
  *   (4, 1), (2, 3), (2, 5); every other d streamed, U = 2 where d/32 is
  *   even, else U = 1.
- * - B = 4: d = 64, 128, 256 -> (2, 5), (2, 9), (2, 17); else (2, 0).
- * - B = 8: d = 32, 64, 128 -> (2, 5), (2, 9), (2, 17); else (2, 0).
+ * - B = 4: d = 64, 128, 256 -> (2, 5), (2, 9), (2, 17); else (2, -1).
+ * - B = 8: d = 32, 64, 128 -> (2, 5), (2, 9), (2, 17); else (2, -1).
+ * - GAMMA_RBQ_TILED, read at every launch, moves the multi-bit shapes:
+ *   1 sends all of them to (2, -1), 0 sends the tiled ones back to the
+ *   streamed (2, 0). B = 1 ignores it. gk::rabitq_scan_is_tiled tells.
  * gk::rabitq_encode: k_rabitq_encode at B = 1, else k_rabitq_encode_ex<B,
  * TR> with TR = 2 (d <= 128), 8 (d <= 512) or 0. gk::rabitq_sval_buckets:
  * k_rabitq_sval_buckets<B>.
@@ -388,7 +391,39 @@ hipError_t gk::rabitq_sval_buckets(hipStream_t s, int nb_bits, int nlist,
  * U = words per load unit (2 at B = 4 and 8, whose entries are whole 8-byte
  * units), NU > 0: the whole entry (code words, A, Mul) is NU units held in
  * registers and double-buffered. NU == 0: the entry is streamed in units of
- * U at consume time and only id and sval are prefetched. */
+ * U at consume time and only id and sval are prefetched.
+ *
+ * NU == -1 (B = 4, 8), the tiled movement, for entries too long for
+ * registers. Streamed, a lane walks its own entry: every load of the wave
+ * touches 64 cache lines and returns to each line once per unit. Tiled, the
+ * WAVE moves its 64 entries together, in slabs of GAMMA_RBQ_TK 8-byte units
+ * per entry, through a tile of its own in LDS (no workgroup barrier):
+ * - pointers: each lane stores its entry pointer into the (still free)
+ *   tile, and lane l reads back those of the entries l / TK + (64 / TK) i,
+ *   i < TK, the ones it loads for;
+ * - gather: load i of a slab takes unit l % TK of entry l / TK + (64 / TK) i
+ *   — TK adjacent lanes cover TK adjacent units, 64 contiguous bytes, so a
+ *   load touches 64 / TK spans instead of 64 lines. The TK loads of slab
+ *   s + 1 are issued into registers before slab s is consumed: registers
+ *   are the second buffer, the tile holds one slab;
+ * - transpose: the units go to row = entry, column = unit of the tile, row
+ *   pitch GAMMA_RBQ_TP = TK + 1 units. The pitch is odd, so the 32 lanes of
+ *   a half-wave read the same column of 32 rows from 32 different bank
+ *   pairs (ds_read_b64, conflict-free), and the writes of a load land on
+ *   l + l / TK, 64 distinct consecutive pairs;
+ * - consume: lane l reads row l and feeds gamma_rbq_ex_word as the other
+ *   movements do, unit u = words 2u (s0) and 2u + 1 (s1). The last slab is
+ *   partial: its lanes past the entry's end load nothing, and its last unit
+ *   is (A, Mul).
+ * Every lane of a wave with one entry to score runs the walk (the loads are
+ * the wave's); only the push is per lane. LDS accesses of one wave execute
+ * in order, so the wave needs no wait between its writes and its reads;
+ * wave_barrier pins the compiler's order. */
+#define GAMMA_RBQ_TK 8
+#define GAMMA_RBQ_TP (GAMMA_RBQ_TK + 1)
+static_assert(64 % GAMMA_RBQ_TK == 0 && GAMMA_RBQ_TP % 2 == 1,
+              "whole slabs per load, odd row pitch");
+
 struct GammaRbqPer {
   float qc2[GAMMA_SCAN_PCH];
   float sqc[GAMMA_SCAN_PCH];
@@ -399,15 +434,16 @@ struct GammaRbqChunk : GammaChunkT<GammaRbqPer> {
 
 template <int U, int NU>
 struct GammaRbqElem {
-  uint32_t w[NU ? U * NU : 1];
-  gamma_gu32p cw; /* NU == 0: the entry's words */
+  uint32_t w[NU > 0 ? U * NU : 1];
+  gamma_gu32p cw; /* NU <= 0: the entry's words */
   uint32_t id;
   float sv, qc2, sqc;
   bool live;
 };
 
 /* dynamic LDS of k_rabitq_scan: `tab` bytes of query table (16 d at B = 1,
- * none otherwise), selector scratch + result, query, chunk */
+ * none otherwise), selector scratch + result, query, chunk, and for the
+ * tiled movement one 64-row tile per wave of the block */
 __host__ __device__ static size_t gamma_rbq_tab_bytes(int nb_bits, int d) {
   return nb_bits == 1 ? (size_t)d * 16 : 0;
 }
@@ -423,9 +459,17 @@ __host__ __device__ static size_t gamma_rbq_chunk_off(size_t tab, int d,
                                                       bool deep = false) {
   return (gamma_rbq_qs_off(tab, k2, deep) + (size_t)d * 4 + 7) / 8 * 8;
 }
-static size_t gamma_rbq_smem(int nb_bits, int d, int k2, bool deep = false) {
-  return gamma_rbq_chunk_off(gamma_rbq_tab_bytes(nb_bits, d), d, k2, deep) +
-         sizeof(GammaRbqChunk);
+static_assert(sizeof(GammaRbqChunk) % 8 == 0, "the tile holds 8-byte units");
+__host__ __device__ static size_t gamma_rbq_tile_off(size_t tab, int d,
+                                                     int k2,
+                                                     bool deep = false) {
+  return gamma_rbq_chunk_off(tab, d, k2, deep) + sizeof(GammaRbqChunk);
+}
+/* tile_bs: the block size of a tiled launch, 0 for the other movements */
+static size_t gamma_rbq_smem(int nb_bits, int d, int k2, bool deep = false,
+                             int tile_bs = 0) {
+  return gamma_rbq_tile_off(gamma_rbq_tab_bytes(nb_bits, d), d, k2, deep) +
+         (size_t)tile_bs * GAMMA_RBQ_TP * 8;
 }
 
 /* B = 1: 8 nibble lookups of one sign word; tab advances by 8 rows */
@@ -515,6 +559,8 @@ k_rabitq_scan(int nq, int S, int d, int nprobe, int k2,
               const int *__restrict__ kill_flag) {
   typedef GammaRbq<B> P;
   static_assert(B == 1 || U == 2, "multi-bit entries move in 8-byte units");
+  static_assert(NU >= -1 && (NU >= 0 || B > 1), "tiled: multi-bit only");
+  constexpr bool TILED = NU < 0;
   extern __shared__ char smem[];
   const size_t tab = gamma_rbq_tab_bytes(B, d);
   [[maybe_unused]] float *lut = (float *)smem; /* B == 1: d/4 x 16 */
@@ -560,9 +606,13 @@ k_rabitq_scan(int nq, int S, int d, int nprobe, int k2,
   const float qq = ch->qq;
   [[maybe_unused]] const float inv_sqrt_d = 1.0f / sqrtf((float)d);
 
-  constexpr int NW = NU ? U * NU : 1; /* NU > 0: words per entry */
-  const int W = NU ? NW - 2 : d / P::DPW;
+  constexpr int NW = NU > 0 ? U * NU : 1; /* NU > 0: words per entry */
+  const int W = NU > 0 ? NW - 2 : d / P::DPW;
   const int EW = W + 2;
+  /* tiled: this wave's tile, 64 rows of GAMMA_RBQ_TP units */
+  [[maybe_unused]] uint64_t *tile =
+      (uint64_t *)(smem + gamma_rbq_tile_off(tab, d, k2, DEEP)) +
+      (threadIdx.x >> 6) * (64 * GAMMA_RBQ_TP);
 
   const int np_sub = sub < nprobe ? (nprobe - sub + S - 1) / S : 0;
   const int *kf = kill_flag ? kill_flag : (const int *)probes;
@@ -691,6 +741,71 @@ k_rabitq_scan(int nq, int S, int d, int nprobe, int k2,
         sel.push(gamma_make_key<IP>(score, e.id));
       }
     };
+    /* the tiled movement (head comment): the wave's 64 entries, slab by
+     * slab, global -> registers -> tile -> the owning lane */
+    auto consume_tiled = [&](const GammaRbqElem<U, NU> &e) {
+      constexpr int K = GAMMA_RBQ_TK, TP = GAMMA_RBQ_TP, EPL = 64 / K;
+      typedef const __attribute__((address_space(1))) gamma_u32x2 *unit_p;
+      retire(e);
+      const bool ok = e.live && !(e.id >> 31) &&
+                      !gamma_bitmap_test(bitmap, (uint64_t)e.id);
+      if (!__ballot(ok)) return; /* wave-uniform: nothing to score */
+      const int lane = (int)(tid & 63u), k = lane % K, g = lane / K;
+      const int nun = W / 2 + 1; /* units of an entry, (A, Mul) last */
+      const int ns = (nun + K - 1) / K, rem = nun - (ns - 1) * K;
+      tile[lane] = (uint64_t)e.cw;
+      __builtin_amdgcn_wave_barrier();
+      unit_p p[K]; /* unit k of the entries this lane loads for */
+#pragma unroll
+      for (int i = 0; i < K; i++)
+        p[i] = (unit_p)(gamma_gu32p)tile[i * EPL + g] + k;
+      __builtin_amdgcn_wave_barrier();
+      uint64_t *wr = tile + g * TP + k;
+      const uint64_t *rd = tile + lane * TP;
+      gamma_u32x2 r[K];
+#pragma unroll
+      for (int i = 0; i < K; i++) r[i] = gamma_u32x2{0u, 0u};
+      /* nothing is read past an entry: the last slab has rem units */
+      auto load = [&](int s) {
+        if (s < ns - 1 || k < rem) {
+#pragma unroll
+          for (int i = 0; i < K; i++) r[i] = p[i][s * K];
+        }
+      };
+      auto store = [&]() {
+#pragma unroll
+        for (int i = 0; i < K; i++)
+          wr[i * EPL * TP] = (uint64_t)r[i].x | ((uint64_t)r[i].y << 32);
+        __builtin_amdgcn_wave_barrier();
+      };
+      auto unit = [&](int u, gamma_cf32p qp, float &s0, float &s1) {
+        const uint64_t v = rd[u];
+        gamma_rbq_ex_word<B>((uint32_t)v, qp, s0);
+        gamma_rbq_ex_word<B>((uint32_t)(v >> 32), qp + P::DPW, s1);
+      };
+      float s0 = 0.0f, s1 = 0.0f;
+      gamma_cf32p qp = qc;
+      load(0);
+      for (int s = 0; s < ns - 1; s++, qp += 2 * K * P::DPW) {
+        store();
+        load(s + 1);
+#pragma unroll
+        for (int u = 0; u < K; u++) unit(u, qp + 2 * u * P::DPW, s0, s1);
+        __builtin_amdgcn_wave_barrier();
+      }
+      store();
+      for (int u = 0; u < rem - 1; u++, qp += 2 * P::DPW) unit(u, qp, s0, s1);
+      const uint64_t f = rd[rem - 1];
+      __builtin_amdgcn_wave_barrier();
+      if (ok) { /* consume's closing at B > 1, operation for operation */
+        const float fa = __uint_as_float((uint32_t)f);
+        const float fm = __uint_as_float((uint32_t)(f >> 32));
+        const float t = fmaf(-P::CB, e.sqc, (s0 + s1) - e.sv);
+        const float pre = fmaf(-2.0f * fm, t, fa + e.qc2);
+        const float score = IP ? -0.5f * (pre - qq) : pre;
+        sel.push(gamma_make_key<IP>(score, e.id));
+      }
+    };
 
     /* flush check, kill poll and the two-set pass loop: the scheme of
      * k_ivfpq_scan's fast path (reasons there) */
@@ -704,7 +819,8 @@ k_rabitq_scan(int nq, int S, int d, int nprobe, int k2,
       const int kv = __hip_atomic_load(kf, __ATOMIC_RELAXED,
                                        __HIP_MEMORY_SCOPE_AGENT);
       fetch(nxt, it_nxt);
-      consume(cur_e);
+      if constexpr (TILED) consume_tiled(cur_e);
+      else consume(cur_e);
       asm volatile("" ::"v"(kv));
       if (!check) return false;
       if (tid == 0) ch->kill[slot] = kill_flag ? kv : 0;
@@ -733,6 +849,25 @@ k_rabitq_scan(int nq, int S, int d, int nprobe, int k2,
   }
 }
 
+/* GAMMA_RBQ_TILED: 1 tiles every multi-bit launch, 0 none (the streamed
+ * movement, for A/B runs and tests); unset or anything else: -1, tiled
+ * where the entry does not fit registers */
+static int gamma_rbq_tiled_knob() {
+  const char *e = getenv("GAMMA_RBQ_TILED");
+  if (e && (e[0] == '0' || e[0] == '1') && !e[1]) return e[0] - '0';
+  return -1;
+}
+/* the multi-bit shapes with a register-resident instantiation */
+static bool gamma_rbq_resident(int nb_bits, int d) {
+  const int W = d * nb_bits / 32;
+  return W == 8 || W == 16 || W == 32;
+}
+bool gk::rabitq_scan_is_tiled(int nb_bits, int d) {
+  if (!gamma_rbq_ok(d, nb_bits) || nb_bits == 1) return false;
+  const int knob = gamma_rbq_tiled_knob();
+  return knob < 0 ? !gamma_rbq_resident(nb_bits, d) : knob == 1;
+}
+
 hipError_t gk::rabitq_scan(hipStream_t s, int nb_bits, int nq, int S, int d,
                            int nprobe, int k2, const float *queries,
                            const float *centroids,
@@ -745,7 +880,9 @@ hipError_t gk::rabitq_scan(hipStream_t s, int nb_bits, int nq, int S, int d,
       k2 > GAMMA_DEEP_MAX_K)
     return hipErrorInvalidValue;
   const bool deep = k2 > 1024;
-  const size_t smem = gamma_rbq_smem(nb_bits, d, k2, deep);
+  const bool tiled = gk::rabitq_scan_is_tiled(nb_bits, d);
+  const size_t smem =
+      gamma_rbq_smem(nb_bits, d, k2, deep, tiled ? gamma_scan_bs() : 0);
   if (smem > 160 * 1024) return hipErrorInvalidValue;
   dim3 g((uint32_t)nq * (uint32_t)S);
   const int W = d * nb_bits / 32; /* code words; the entry is W + 2 */
@@ -775,6 +912,8 @@ hipError_t gk::rabitq_scan(hipStream_t s, int nb_bits, int nq, int S, int d,
           else if (W == 8) launch(gamma_c<2>(), gamma_c<5>()); /* 40 */
           else if (W % 2 == 0) launch(gamma_c<2>(), gamma_c<0>());
           else launch(gamma_c<1>(), gamma_c<0>());
+        } else if (tiled) {
+          launch(gamma_c<2>(), gamma_c<-1>());
         } else { /* 40, 72 and 136 bytes in registers */
           if (!gamma_pick<8, 16, 32>(W, [&](auto w) {
                 launch(gamma_c<2>(), gamma_c<decltype(w)::value / 2 + 1>());

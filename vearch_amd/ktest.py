@@ -71,6 +71,7 @@ def _lib():
         L.GammaKTestRabitqScan.argtypes = [
             i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, i32, vp,
             vp]
+        L.GammaKTestRabitqScanIsTiled.argtypes = [i32, i32]
         L.GammaKTestIvfflatScan.argtypes = [
             i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp]
         L.GammaKTestPqTablesB.argtypes = [i32, i32, i32, i32, vp, vp, vp]
@@ -1021,14 +1022,18 @@ def rabitq_scan(lists, probes, queries, centroids, S, k2, ip, bitmap=None,
     centroids float32 (nlist, d); bitmap: optional uint32 words; kill_flag:
     see _kill_dev.
     Returns (keys uint64 (nq, S, k2), scores, ids): the raw partial rows
-    and their gk::sort_rows merge to the top-k2 (-1 / -1 padded)."""
+    and their gk::sort_rows merge to the top-k2 (-1 / -1 padded).
+    k2 > 1024 (the deep selector): the launch gets its regions of 4 * k2
+    keys per row; keys is their first k2 slots, unsorted, and scores / ids
+    are None, None (merge keys with select_deep)."""
     f32 = lambda a: torch.from_numpy(  # noqa: E731
         np.ascontiguousarray(a, dtype=np.float32).copy()).cuda()
     q_d, c_d = f32(queries), f32(centroids)
     nq, d = q_d.shape
     nlist = len(lists)
     assert c_d.shape == (nlist, d) and d % 32 == 0
-    assert S * k2 <= 2048
+    deep = k2 > 1024
+    assert deep or S * k2 <= 2048
     cs = d * nb_bits // 8 + 8
     probes = np.ascontiguousarray(probes, dtype=np.int64)
     nprobe = probes.shape[1]
@@ -1048,12 +1053,20 @@ def rabitq_scan(lists, probes, queries, centroids, S, k2, ip, bitmap=None,
     bk_d = torch.tensor(rows, dtype=torch.int64).reshape(-1, 4).cuda()
     bm_d = None if bitmap is None else bitmap_to_dev(bitmap)
     kf_d = _kill_dev(kill_flag)
-    keys = torch.full((nq, S, k2), 0x5A5A5A5A5A5A5A5A, dtype=torch.int64,
-                      device="cuda")
+    keys = torch.full((nq, S, 4 * k2 if deep else k2), 0x5A5A5A5A5A5A5A5A,
+                      dtype=torch.int64, device="cuda")
     _call("GammaKTestRabitqScan", nb_bits, nq, S, d, nprobe, k2, _p(q_d),
           _p(c_d),
           _p(bk_d, torch.int64), nlist, _p(pr_d, torch.int64),
           _p(bm_d, torch.int32), int(bool(ip)), _p(keys, torch.int64),
           _p(kf_d, torch.int32))
+    if deep:
+        return keys_to_np(keys[:, :, :k2].contiguous()), None, None
     od, oi = sort_rows(keys.reshape(nq, S * k2), k2, ip)
     return keys_to_np(keys), od.cpu().numpy(), oi.cpu().numpy()
+
+
+def rabitq_scan_is_tiled(nb_bits, d):
+    """gk::rabitq_scan_is_tiled under the current GAMMA_RBQ_TILED: whether
+    a rabitq_scan launch of this shape moves its entries through LDS."""
+    return _lib().GammaKTestRabitqScanIsTiled(nb_bits, d) == 1
