@@ -330,6 +330,18 @@ int GammaKTestSelectDeep(int nq, int S, int k2, int64_t stride, int kout,
                          const uint64_t *keys, uint64_t *out);
 int GammaKTestDeepSelectorProbe(int n, int k2, const uint64_t *keys,
                                 uint64_t *region);
+/* filter-first (kernels.h): gk::bitmap_candidates compacts the clear bits
+ * of an exclusion bitmap over [0, n) into ascending ids (out_ids, at most
+ * cap written; *count, device, counts all; block_tmp one u32 per 8192 ids);
+ * gk::cand_scan writes the nq x ncand_pad key matrix of nq queries against
+ * one shared candidate list, EMPTY beyond ncand. */
+int GammaKTestBitmapCandidates(const uint32_t *bitmap, int64_t n,
+                               uint32_t *out_ids, int64_t cap,
+                               uint32_t *block_tmp, int *count);
+int GammaKTestCandScan(int nq, int ncand, int64_t ncand_pad, int d,
+                       const float *queries, const uint32_t *cand,
+                       const float *const *segs, int n_segs, int seg_shift,
+                       int ip, uint64_t *out_keys);
 
 #ifdef __cplusplus
 }

@@ -4,6 +4,7 @@ tag field, protobuf Search with a term filter at several selectivities,
 wall-clock per batch. Run on a GPU box:
 
     python tools/filter_probe.py
+    python tools/filter_probe.py --filter-first profiles/filter_first.json
 """
 import os
 import struct
@@ -57,5 +58,79 @@ def main():
     eng.close()
 
 
+def filter_first_probe(out_path, steps=9):
+    """The same range-filtered request with `filter_first` on and off,
+    alternating in one process, on an IVFPQ and a FLAT table of the data
+    above. Per (table, selectivity, mode): medians and min-max over `steps`
+    of the scan time (last_timing scan_us) and the wall step time of one
+    64-query protobuf Search, results per query, and recall@10 against the
+    fp64 top-10 of the matching docs."""
+    import json
+
+    import numpy as np
+
+    n, d, nq, k = 400_000, 64, 64, 10
+    base = orc.gen_clustered(n, d, seed=42, ncl=2000)
+    q = orc.gen_queries(base, nq, seed=5)
+    tags = np.arange(n) % 1000
+    widths = (1, 10, 20, 50, 100, 200, 500)  # of 1000 tags: 0.1 % .. 50 %
+    truth = {w: np.flatnonzero(tags < w) for w in widths}
+    truth = {w: m[orc.flat_topk_f64(base[m], q, k)[1]]
+             for w, m in truth.items()}
+    tables = {
+        "IVFPQ": '{"ncentroids": 512, "nsubvector": 16, "metric_type": "L2", '
+                 '"training_threshold": 80000}',
+        "FLAT": '{"metric_type": "L2"}',
+    }
+    rows = []
+    for kind, params in tables.items():
+        eng = GammaEngine(path="/tmp/gamma_ffprobe_" + kind)
+        eng.create_table(d, kind, params,
+                         scalar_fields=[("tag", fbsenc.DATA_INT)])
+        for vid in range(n):
+            eng.add_doc(str(vid), base[vid],
+                        fields=[("tag", struct.pack("<i", int(tags[vid])),
+                                 fbsenc.DATA_INT)])
+        eng.build_index()
+        for w in widths:
+            rf = [("tag", struct.pack("<i", 0), struct.pack("<i", w - 1),
+                   True, True)]
+            modes = {"off": '{"nprobe": 32}',
+                     "on": '{"nprobe": 32, "filter_first": 1048576}'}
+            acc = {m: {"scan_us": [], "step_ms": []} for m in modes}
+            for m, ip in modes.items():  # warm both paths
+                eng.search_pb(q, topn=k, index_params=ip, range_filters=rf)
+            for _ in range(steps):
+                for m, ip in modes.items():
+                    t = time.perf_counter()
+                    res = eng.search_pb(q, topn=k, index_params=ip,
+                                        range_filters=rf)
+                    acc[m]["step_ms"].append((time.perf_counter() - t) * 1e3)
+                    acc[m]["scan_us"].append(eng.last_timing()["scan_us"])
+                    acc[m]["res"] = res
+            for m in modes:
+                ids = [[int(it["fields"]["_id"]) for it in r["items"]]
+                       for r in acc[m]["res"]]
+                hit = sum(len(set(g.tolist()) & set(r))
+                          for g, r in zip(truth[w], ids))
+                row = {"table": kind, "candidates": n * w // 1000,
+                       "filter_first": m, "steps": steps,
+                       "results_per_query": sum(map(len, ids)) / nq,
+                       "recall_at_10": hit / (nq * k)}
+                for key in ("scan_us", "step_ms"):
+                    v = sorted(acc[m][key])
+                    row[key] = {"median": v[len(v) // 2], "min": v[0],
+                                "max": v[-1]}
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+        eng.close()
+    with open(out_path, "w") as f:
+        json.dump({"n": n, "d": d, "nq": nq, "topn": k, "nprobe": 32,
+                   "rows": rows}, f, indent=1)
+
+
 if __name__ == "__main__":
-    main()
+    if len(sys.argv) == 3 and sys.argv[1] == "--filter-first":
+        filter_first_probe(sys.argv[2])
+    else:
+        main()

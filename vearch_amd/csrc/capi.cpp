@@ -496,13 +496,17 @@ static struct CStatus Search_unguarded(void *engine, const char *request_str, in
   if (nq <= 0) return err_status(1, "Search n shouldn't less than 0!");
 
   /* retrieval params JSON (ivfpq.cc:233-294): nprobe, recall_num,
-   * metric_type, parallel_on_queries (N/A on GPU) */
-  int nprobe = 0, recall_num = 0, metric = 0;
+   * metric_type, parallel_on_queries (N/A on GPU); filter_first: the
+   * candidate count up to which a filtered request takes the filter-first
+   * plan (absent or <= 0: off; the reference's disable_filter_first is
+   * the opt-out form of the same switch on its FLAT index) */
+  int nprobe = 0, recall_num = 0, metric = 0, filter_first = 0;
   if (!req.index_params.empty()) {
     gjson::Value v;
     if (gjson::parse(req.index_params, v)) {
       v.get_int("nprobe", nprobe);
       v.get_int("recall_num", recall_num);
+      v.get_int("filter_first", filter_first);
       std::string mt;
       if (v.get_str("metric_type", mt)) {
         /* only the metric names the reference knows (ivfpq.cc:253-257,
@@ -541,7 +545,7 @@ static struct CStatus Search_unguarded(void *engine, const char *request_str, in
                      recall_num, metric, req.brute == 1, req.request_id,
                      req.partition_id, dists.data(), ids.data(),
                      req.l2_sqrt, &terms, &ranges, &ferr, req.op,
-                     /*prelocked=*/true);
+                     /*prelocked=*/true, filter_first);
   if (rc == -2) return err_status(-2, "request killed");
   if (rc == -3) return err_status(1, ferr);
   if (rc != 0) return err_status(1, "search failed");

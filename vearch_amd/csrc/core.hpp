@@ -259,6 +259,12 @@ struct SearchScratch {
   /* deep top-k (k2 > 1024): the selectors' regions of one query group, and
    * the sorted keys of the final gk::select_deep */
   DeviceBuf deep_regions, deep_keys;
+  /* what build_filter_bitmap_ left in filt_host: the ids it covers and how
+   * many of them survive (live and passing the filter) */
+  int64_t filt_n = 0, filt_pass = 0;
+  /* filter-first plan: the surviving ids, gk::bitmap_candidates' block
+   * offsets and device count, and one query group's key matrix */
+  DeviceBuf ff_cand, ff_blocks, ff_count, ff_keys;
   bool in_use = false;
   ~SearchScratch() {
     if (stream) (void)hipStreamDestroy(stream);
@@ -555,7 +561,13 @@ class Engine {
   /* the hot path: batched vector search.
    * metric: 0 default, 1 L2, 2 IP. Returns 0 ok, -2 killed, <0 error.
    * xq == nullptr -> use the cached device-resident queries (bench path,
-   * nq must equal the cached count). */
+   * nq must equal the cached count).
+   * filter_first > 0 (search param of the same name): a filtered request
+   * whose filter leaves at most min(filter_first, kFilterFirstMax) live
+   * documents scans exactly those against the raw store (DESIGN.md
+   * "Filter-first") instead of walking the index; the result is the exact
+   * top-k of the live matching documents. Not for BINARYIVF. */
+  static constexpr int64_t kFilterFirstMax = (int64_t)1 << 20;
   int search(int nq, const float *xq, int k, int nprobe, int recall_num,
              int metric, bool brute_force, const std::string &request_id,
              int partition_id, float *out_dists, int64_t *out_ids,
@@ -563,7 +575,7 @@ class Engine {
              const std::vector<TermFilterSpec> *term_filters = nullptr,
              const std::vector<RangeFilterSpec> *range_filters = nullptr,
              std::string *filter_err = nullptr, int filter_op = 0,
-             bool prelocked = false);
+             bool prelocked = false, int filter_first = 0);
 
   /* Shared (read) lock on the engine. The C ABI takes this across
    * Search/Query/GetDoc* response assembly so the doc/table state read

@@ -750,8 +750,15 @@ int Engine::build_filter_bitmap_(const std::vector<TermFilterSpec> &terms,
   }
 
   sc.filt_host.assign((size_t)words, 0);
-  for (int64_t w = 0; w < words; w++)
-    sc.filt_host[w] = ~inc[w] | bitmap_.host_word(w);
+  int64_t dropped = 0; /* among ids [0, n): the filter-first plan's count */
+  for (int64_t w = 0; w < words; w++) {
+    const uint32_t x = ~inc[w] | bitmap_.host_word(w);
+    sc.filt_host[w] = x;
+    dropped += __builtin_popcount(
+        (w == words - 1 && (n & 31)) ? x & ((1u << (n & 31)) - 1) : x);
+  }
+  sc.filt_n = n;
+  sc.filt_pass = n - dropped;
   if (!dev_out) return 0; /* browse path: host bitmap only */
   if (sc.filt_dev.reserve((size_t)std::max<int64_t>(words, 1) * 4))
     return -1;
@@ -798,7 +805,8 @@ int Engine::search(int nq, const float *xq, int k, int nprobe,
                    float *out_dists, int64_t *out_ids, bool l2_sqrt,
                    const std::vector<TermFilterSpec> *term_filters,
                    const std::vector<RangeFilterSpec> *range_filters,
-                   std::string *filter_err, int filter_op, bool prelocked) {
+                   std::string *filter_err, int filter_op, bool prelocked,
+                   int filter_first) {
   if (!table_created_ || nq <= 0 || k <= 0) return -1;
   /* Concurrent searches: each takes the read lock (Add/Build/Load are
    * write-locked) plus one SearchScratch context from the pool — its
@@ -894,10 +902,53 @@ int Engine::search(int nq, const float *xq, int k, int nprobe,
       return -3;
   }
 
+  /* filter-first plan (PlanBitmapScan, gamma_index_flat.cc:325; DESIGN.md
+   * "Filter-first"): the filter leaves few enough documents to score them
+   * all, exactly, against the raw store. Opt-in per request; every table
+   * kind with float vectors, trained or not. */
+  const bool ff =
+      have_filters && !bin && filter_first > 0 && dim_ % 4 == 0 &&
+      sc.filt_n <= raw_.size() &&
+      sc.filt_pass <= std::min<int64_t>(filter_first, kFilterFirstMax);
+
   double t_assign = 0, t_scan = 0;
   bool need_canonical_rerank = true; /* FLAT & IVFFLAT canonicalize */
   bool fused = false; /* re-rank + top-k done inside the scan kernel */
-  if (use_flat && bin) {
+  if (ff) {
+    /* 1. the surviving ids, ascending, from the bitmap just uploaded (their
+     *    number is known from the host popcount: no sync);
+     * 2. per query group, the nq x ncand_pad matrix of exact keys and its
+     *    sorted top-k. A group's matrix stays within kDeepRegionCapBytes. */
+    const int ncand = (int)sc.filt_pass;
+    const int64_t ncand_pad = std::max<int64_t>(
+        k, ((int64_t)ncand + gk::CAND_SCAN_PAD - 1) / gk::CAND_SCAN_PAD *
+               gk::CAND_SCAN_PAD);
+    const int64_t nblk =
+        (sc.filt_n + gk::BITMAP_CAND_BLOCK - 1) / gk::BITMAP_CAND_BLOCK;
+    const int gq = (int)std::min<int64_t>(
+        nq, std::max<int64_t>(
+                1, (int64_t)IVFIndex::kDeepRegionCapBytes / (ncand_pad * 8)));
+    if (sc.ff_cand.reserve((size_t)std::max(ncand, 1) * 4) ||
+        sc.ff_blocks.reserve((size_t)std::max<int64_t>(nblk, 1) * 4) ||
+        sc.ff_count.reserve(4) ||
+        sc.ff_keys.reserve((size_t)gq * ncand_pad * 8) ||
+        sc.deep_keys.reserve((size_t)nq * k * 8))
+      return -1;
+    tm.rec(5);
+    GAMMA_CHECK(gk::bitmap_candidates(
+        s, bm, sc.filt_n, sc.ff_cand.as<uint32_t>(), ncand,
+        sc.ff_blocks.as<uint32_t>(), sc.ff_count.as<int>()));
+    for (int g0 = 0; g0 < nq; g0 += gq) {
+      const int gn = std::min(gq, nq - g0);
+      GAMMA_CHECK(gk::cand_scan(
+          s, gn, ncand, ncand_pad, dim_, qptr + (size_t)g0 * dim_,
+          sc.ff_cand.as<uint32_t>(), raw_.dev_seg_table(), raw_.num_segs(),
+          RawStore::SEG_SHIFT, ip, sc.ff_keys.as<uint64_t>()));
+      GAMMA_CHECK(gk::select_deep(
+          s, gn, 1, (int)ncand_pad, ncand_pad, k, sc.ff_keys.as<uint64_t>(),
+          sc.deep_keys.as<uint64_t>() + (size_t)g0 * k));
+    }
+  } else if (use_flat && bin) {
     /* exact Hamming top-k over the raw store: integer distances, so no
      * margin and no canonical re-rank */
     GAMMA_CHECK(gk::hamming_flat_scan(
@@ -966,7 +1017,13 @@ int Engine::search(int nq, const float *xq, int k, int nprobe,
   tm.rec(2);
   if (KillRegistry::inst().killed(request_id, pid)) return -2;
 
-  if (deep) {
+  if (ff) {
+    /* exact keys already, sorted per query, EMPTY where fewer than k match */
+    GAMMA_CHECK(gk::unpack_keys(s, (int64_t)nq * k,
+                                sc.deep_keys.as<uint64_t>(), ip,
+                                sc.out_d.as<float>(),
+                                sc.out_i.as<int64_t>()));
+  } else if (deep) {
     /* gk::rerank tiles any ncand; its keys go to gk::select_deep for the
      * final top-k, sort_rows' LDS row being sized for 2048. Without the
      * re-rank leg k == k2 and the merged row is the result. */
@@ -1011,8 +1068,9 @@ int Engine::search(int nq, const float *xq, int k, int nprobe,
   {
     std::lock_guard<std::mutex> lk(timing_mu_);
     last_timing[0] = tm.ms(0, 1) * 1000.0;
-    last_timing[1] = (use_flat ? 0.0 : t_assign) * 1000.0;
-    last_timing[2] = (use_flat ? tm.ms(1, 2) : t_scan) * 1000.0;
+    last_timing[1] = (use_flat || ff ? 0.0 : t_assign) * 1000.0;
+    last_timing[2] =
+        (ff ? tm.ms(5, 2) : use_flat ? tm.ms(1, 2) : t_scan) * 1000.0;
     last_timing[3] = tm.ms(2, 3) * 1000.0;
     last_timing[4] = tm.ms(3, 4) * 1000.0;
     last_timing[5] = tm.ms(0, 4) * 1000.0;

@@ -441,4 +441,35 @@ hipError_t rabitq_scan(hipStream_t s, int nb_bits, int nq, int S, int d,
  * does not enter the scores. */
 bool rabitq_scan_is_tiled(int nb_bits, int d);
 
+/* ---- filter-first (filter_first_kernels.hpp, DESIGN.md "Filter-first") */
+
+/* Ordered stream compaction of an exclusion bitmap (u32 words, bit set =
+ * dropped) over ids [0, n), n < 2^31: out_ids[0, *count) = the ids whose bit
+ * is clear, ascending; *count (device) = how many there are. Bits at or
+ * beyond n in the last word are ignored. n == 0 and an all-set bitmap give
+ * *count = 0. Ids past slot `cap` are counted and not written. block_tmp:
+ * one u32 per BITMAP_CAND_BLOCK ids (rounded up), device scratch. */
+enum { BITMAP_CAND_BLOCK = 8192 };
+hipError_t bitmap_candidates(hipStream_t s, const uint32_t *bitmap, int64_t n,
+                             uint32_t *out_ids, int64_t cap,
+                             uint32_t *block_tmp, int *count);
+
+/* Exact distances of nq queries x ONE shared candidate list:
+ *   out_keys[q * ncand_pad + c] = gamma_make_key<ip>(dist(q, cand[c]),
+ *                                                    cand[c]),  c < ncand
+ * and GAMMA_KEY_EMPTY for ncand <= c < ncand_pad, the form gk::select_deep
+ * takes (S = 1, k2 = stride = ncand_pad). dist is gk::rerank's fmaf chain,
+ * bit for bit, so the keys equal gk::rerank's on the same pairs. Candidate
+ * rows are gathered through the raw-store segment table as in gk::rerank;
+ * an id beyond the table gives EMPTY. d % 4 == 0, anything else is
+ * hipErrorInvalidValue and launches nothing. A batch of at most
+ * CAND_SCAN_NARROW_NQ queries runs the 8 x 256 tile, larger ones 64 x 64;
+ * keys do not depend on it. CAND_SCAN_PAD, the wider candidate tile, is
+ * what callers round ncand_pad up to. */
+enum { CAND_SCAN_NARROW_NQ = 8, CAND_SCAN_PAD = 256 };
+hipError_t cand_scan(hipStream_t s, int nq, int ncand, int64_t ncand_pad,
+                     int d, const float *queries, const uint32_t *cand,
+                     const float *const *segs, int n_segs, int seg_shift,
+                     bool ip, uint64_t *out_keys);
+
 }  // namespace gk

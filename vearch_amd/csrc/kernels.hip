@@ -1799,3 +1799,6 @@ hipError_t gk::pq_encode_pack4(hipStream_t s, int64_t n, int d, int M,
 
 /* IVFRABITQ, nb_bits 1, 4 and 8: encode, sval rebuild, list scan */
 #include "rabitq_kernels.hpp"
+
+/* filter-first: bitmap compaction and the shared-candidate exact scan */
+#include "filter_first_kernels.hpp"

@@ -322,4 +322,20 @@ int GammaKTestDeepSelectorProbe(int n, int k2, const uint64_t *keys,
   return kt_done(gk::deep_selector_probe(nullptr, n, k2, keys, region));
 }
 
+int GammaKTestBitmapCandidates(const uint32_t *bitmap, int64_t n,
+                               uint32_t *out_ids, int64_t cap,
+                               uint32_t *block_tmp, int *count) {
+  return kt_done(gk::bitmap_candidates(nullptr, bitmap, n, out_ids, cap,
+                                       block_tmp, count));
+}
+
+int GammaKTestCandScan(int nq, int ncand, int64_t ncand_pad, int d,
+                       const float *queries, const uint32_t *cand,
+                       const float *const *segs, int n_segs, int seg_shift,
+                       int ip, uint64_t *out_keys) {
+  return kt_done(gk::cand_scan(nullptr, nq, ncand, ncand_pad, d, queries,
+                               cand, segs, n_segs, seg_shift, ip != 0,
+                               out_keys));
+}
+
 } /* extern "C" */

@@ -90,6 +90,9 @@ def _lib():
             i32, i64, i32, i32, i32, c.POINTER(c.c_int)]
         L.GammaKTestSelectDeep.argtypes = [i32, i32, i32, i64, i32, vp, vp]
         L.GammaKTestDeepSelectorProbe.argtypes = [i32, i32, vp, vp]
+        L.GammaKTestBitmapCandidates.argtypes = [vp, i64, vp, i64, vp, vp]
+        L.GammaKTestCandScan.argtypes = [
+            i32, i32, i64, i32, vp, vp, vp, i32, i32, i32, vp]
         _ready = True
     return L
 
@@ -304,6 +307,46 @@ def deep_selector(keys, k2):
     _call("GammaKTestSelectDeep", 1, 1, k2, 4 * k2, k2,
           _p(region, torch.int64), _p(out, torch.int64))
     return keys_to_np(out)[0]
+
+
+BITMAP_CAND_BLOCK = 8192  # ids per compaction block (kernels.h)
+
+
+def bitmap_candidates(words_u32, n, cap=None):
+    """gk::bitmap_candidates: exclusion bitmap (numpy uint32 words) over ids
+    [0, n) -> (ids numpy uint32 of length cap, count). cap defaults to n;
+    slots the kernel did not write keep the fill 0xA5A5A5A5."""
+    cap = n if cap is None else cap
+    words = np.ascontiguousarray(words_u32, dtype=np.uint32)
+    assert words.shape[0] * 32 >= n
+    bm = bitmap_to_dev(words) if words.shape[0] else None
+    out = torch.full((max(cap, 1),), 0xA5A5A5A5 - (1 << 32),
+                     dtype=torch.int32, device="cuda")
+    nblk = (n + BITMAP_CAND_BLOCK - 1) // BITMAP_CAND_BLOCK
+    tmp = torch.full((max(nblk, 1),), -7, dtype=torch.int32, device="cuda")
+    count = torch.full((1,), -7, dtype=torch.int32, device="cuda")
+    _call("GammaKTestBitmapCandidates", _p(bm, torch.int32), n, _p(out), cap,
+          _p(tmp), _p(count))
+    return out.cpu().numpy().view(np.uint32)[:cap], int(count.item())
+
+
+def cand_scan(queries, segs, seg_shift, ip, cand_u32, ncand_pad=None):
+    """gk::cand_scan: queries (nq, d) device f32, cand numpy uint32 ids into
+    the segment list `segs` -> (nq, ncand_pad) device int64 key matrix,
+    pre-filled with a pattern so an unwritten slot shows."""
+    assert queries.is_contiguous()
+    nq, d = queries.shape
+    cand = np.ascontiguousarray(cand_u32, dtype=np.uint32)
+    ncand = cand.shape[0]
+    ncand_pad = ncand if ncand_pad is None else ncand_pad
+    table = seg_table(segs)
+    c_d = torch.from_numpy(cand.view(np.int32).copy()).cuda()
+    out = torch.full((nq, ncand_pad), 0x5A5A5A5A5A5A5A5A, dtype=torch.int64,
+                     device="cuda")
+    _call("GammaKTestCandScan", nq, ncand, ncand_pad, d,
+          _p(queries, torch.float32), _p(c_d, torch.int32), _p(table),
+          len(segs), seg_shift, int(bool(ip)), _p(out, torch.int64))
+    return out
 
 
 def coarse_can_filter(nq, nlist, d, nprobe, n1=0):
