@@ -221,6 +221,31 @@ int GammaKTestIvfpqScanRerank(int nq, int S, int d, int M, int ksub,
                               int seg_shift, int k, float *out_dists,
                               int64_t *out_ids);
 int GammaKTestIvfpqScanCanFuseRerank(int d, int M, int ksub, int k2, int S);
+/* IvfpqScanRerank with the pruning block of gk::ivfpq_scan (kernels.h,
+ * GammaScanPrune): rmax nlist floats, qnorms nq, cnorms nlist; stats 0 or
+ * 3 * nq zeroed ints (the counting kernel; refused together with with_rr).
+ * GAMMA_SCAN_PRUNE / GAMMA_SCAN_PRUNE_HEAD are read by the launch. */
+int GammaKTestIvfpqScanPrune(int nq, int S, int d, int M, int ksub,
+                             int nprobe, int k2, const float *queries,
+                             const float *centroids, const float *codebooks,
+                             const float *atab, const float *cwn,
+                             const float *probe_dists,
+                             const void *buckets_dev, int nlist,
+                             const int64_t *probes, const uint32_t *bitmap,
+                             int ip, uint64_t *out_keys,
+                             const int *kill_flag, const int32_t *qmap,
+                             int with_rr, const float *rr_queries,
+                             const float *const *segs, int n_segs,
+                             int seg_shift, int k, float *out_dists,
+                             int64_t *out_ids, const float *rmax,
+                             const float *qnorms, const float *cnorms,
+                             int *stats);
+/* gk::pq_list_rmax: bks_dev 0 = the n staged entries `codes` with list
+ * numbers asg (0: every entry in asg_const); else the buckets' entries. */
+int GammaKTestPqListRmax(int64_t n, int M, int ksub, int nlist,
+                         const uint8_t *codes, const int32_t *asg,
+                         int asg_const, const void *bks_dev,
+                         const float *cwn, float *rmax);
 /* The sliced-table scan (k_ivfpq_scan_wide, kernels.h "Wide tables") reads
  * atab for both metrics: PqTablesIp is gk::pq_tables_ip, the inner-product
  * table (nq x M x 256). IvfpqWideInfo: out5 = {sub-quantizers per table

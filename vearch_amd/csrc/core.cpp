@@ -754,6 +754,7 @@ int IVFIndex::train(const float *xt, int64_t n, hipStream_t s,
                         codebooks_.as<float>(),
                         btable_.as<float>()) != hipSuccess)
       return -1;
+    if (reset_rmax_(s)) return -1;
   }
   dead_.assign(nlist_, 0); /* a fresh model starts with no dead entries */
   dead_total_ = 0;
@@ -846,6 +847,23 @@ int IVFIndex::update_cwn_(hipStream_t s) {
   if (cwn_.reserve((size_t)M_ * ksub_ * 4)) return -1;
   GAMMA_CHECK(gk::pq_cwn(s, M_, ksub_, dsub_, codebooks_.as<float>(),
                          cwn_.as<float>()));
+  return 0;
+}
+
+/* residual radii follow the codebooks and the lists: zero, then the maximum
+ * over whatever the buckets hold (train on a filled index, load) */
+int IVFIndex::reset_rmax_(hipStream_t s) {
+  if (rmax_.reserve((size_t)nlist_ * 4)) return -1;
+  GAMMA_CHECK(hipMemsetAsync(rmax_.get(), 0, (size_t)nlist_ * 4, s));
+  bool any = false;
+  for (const Bucket &bk : buckets_) any = any || bk.size > 0;
+  if (any) {
+    if (update_dev_buckets(s)) return -1;
+    GAMMA_CHECK(gk::pq_list_rmax(s, 0, M_, ksub_, nlist_, nullptr, nullptr, 0,
+                                 dev_buckets_.as<GammaBucketDev>(),
+                                 cwn_.as<float>(), rmax_.as<float>()));
+  }
+  GAMMA_CHECK(hipStreamSynchronize(s));
   return 0;
 }
 
@@ -1040,15 +1058,38 @@ int IVFIndex::add(const float *x_host, const int64_t *vids, int64_t n,
       std::vector<float> svals;
     };
     std::map<int32_t, Group> groups;
+    bool asg_fixed = false;
     for (int64_t i = 0; i < cn; i++) {
       int32_t b = asg_h[i];
-      if (b < 0 || b >= nlist_) b = (int32_t)(vids[c0 + i] % nlist_);
+      if (b < 0 || b >= nlist_) {
+        /* a row the assignment could not place (non-finite values): filed
+         * under vid % nlist with a residual and an S term (0) that belong
+         * to no list. The scan's list bound rests on dis = ||q - c - r||^2,
+         * which does not hold for such an entry; its distance is
+         * meaningless with or without the bound, and the bound may skip it
+         * where the plain walk would have scored it. */
+        b = (int32_t)(vids[c0 + i] % nlist_);
+        asg_h[i] = b;
+        asg_fixed = true;
+      }
       auto &g = groups[b];
       g.ids.push_back((uint32_t)vids[c0 + i]); /* vid < 2^31 enforced */
       size_t off = g.data.size();
       g.data.resize(off + entry);
       memcpy(g.data.data() + off, payload_h + (size_t)i * entry, entry);
       if (pq) g.svals.push_back(sterm_h[i]);
+    }
+    if (params_.kind == IndexKind::IVFPQ) {
+      /* raise the radius of every list that receives an entry, by the list
+       * numbers the entries are filed under; ordered on s in front of the
+       * scatter's synchronise, like it */
+      if (asg_fixed)
+        GAMMA_CHECK(hipMemcpy(asg.get(), asg_h.data(), (size_t)cn * 4,
+                              hipMemcpyHostToDevice));
+      GAMMA_CHECK(gk::pq_list_rmax(s, cn, M_, ksub_, nlist_,
+                                   codes.as<uint8_t>(), asg.as<int32_t>(), 0,
+                                   nullptr, cwn_.as<float>(),
+                                   rmax_.as<float>()));
     }
     /* capacity pass, then ONE staged upload + scatter kernel for the
      * whole chunk (3 tiny hipMemcpys per bucket per chunk were the
@@ -1196,6 +1237,13 @@ int IVFIndex::prepare_fast_one(const float *vec_h, hipStream_t s,
     if (gk::pq_sterm(s, 1, M_, ksub_, nlist_, codes.as<uint8_t>(),
                      asg.as<int32_t>(), 0, btable_.as<float>(),
                      sterm.as<float>()) != hipSuccess)
+      return -1;
+    /* the list's radius rises here, in front of the synchronise and so in
+     * front of commit_fast_one's publication of the new size: a concurrent
+     * search never sees the entry under a radius that does not cover it */
+    if (gk::pq_list_rmax(s, 1, M_, ksub_, nlist_, codes.as<uint8_t>(),
+                         asg.as<int32_t>(), 0, nullptr, cwn_.as<float>(),
+                         rmax_.as<float>()) != hipSuccess)
       return -1;
     GAMMA_CHECK(hipStreamSynchronize(s));
     GAMMA_CHECK(hipMemcpy(code_out, codes.get(), (size_t)code_size_,
@@ -1573,9 +1621,16 @@ int IVFIndex::search(const float *q_dev, int nq, int k2, int nprobe,
     const bool fuse =
         rr && fused && gk::ivfpq_scan_can_fuse_rerank(d_, M_, ksub_, k2, S);
     if (fuse) *fused = true;
+    /* the list bound (gk::ivfpq_scan 5): the launcher applies it where its
+     * kernel has it; q_norms_dev are the norms of the scan's own queries
+     * (the rotated ones under OPQ) */
+    const bool prune = !metric_ip && q_norms_dev && rmax_.get();
     for (int g0 = 0; g0 < nq; g0 += gq) {
       const int gn = std::min(gq, nq - g0);
       const float *qg = q_dev + (size_t)g0 * d_;
+      const GammaScanPrune pg = {rmax_.as<float>(),
+                                 prune ? q_norms_dev + g0 : nullptr,
+                                 cent_norms_.as<float>(), nullptr};
       GammaScanRerank rg;
       if (fuse) {
         rg = *rr;
@@ -1602,7 +1657,7 @@ int IVFIndex::search(const float *q_dev, int nq, int k2, int nprobe,
           dev_buckets_.as<GammaBucketDev>(), nlist_,
           sc.probes.as<int64_t>() + (size_t)g0 * nprobe, bitmap_dev,
           metric_ip, out_keys_dev + (size_t)g0 * S * k2, kill_flag_dev,
-          qmap_dev, fuse ? &rg : nullptr));
+          qmap_dev, fuse ? &rg : nullptr, prune ? &pg : nullptr));
     }
   } else if (rabitq()) {
     /* the factor A in the entries was encoded for the table's metric; a
@@ -1849,6 +1904,7 @@ int IVFIndex::load(FILE *f, hipStream_t s, std::string *err) {
                              btable_.as<float>()) != hipSuccess)
       return -1;
     GAMMA_CHECK(hipStreamSynchronize(s));
+    if (reset_rmax_(s)) return -1; /* rebuilt like the S terms, not dumped */
   } else if (rabitq()) {
     if (gk::rabitq_sval_buckets(s, params_.nb_bits, nlist_, d_,
                                 dev_buckets_.as<GammaBucketDev>(),

@@ -426,7 +426,15 @@ class IVFIndex {
                         from codebooks_ wherever those are written, never
                         dumped */
   int update_cwn_(hipStream_t s);
-  DeviceBuf opq_R_;  /* d x d rotation, row-major: y_j = R[j] . x */
+  /* IVFPQ: per-list residual radius, nlist f32 (gk::pq_list_rmax): an upper
+   * bound on the decoded-residual norm of every entry of the list, which the
+   * L2 scan's list bound reads. Zeroed and rebuilt from the buckets by
+   * reset_rmax_ wherever a model arrives (train, load); raised by every
+   * append before the entry is published; left alone by del and compact,
+   * which can only make it loose. Never dumped. */
+  DeviceBuf rmax_;
+  int reset_rmax_(hipStream_t s);
+  DeviceBuf opq_R_; /* d x d rotation, row-major: y_j = R[j] . x */
   std::vector<float> opq_R_host_;
   struct Bucket {
     std::unique_ptr<DeviceBuf> ids, data;

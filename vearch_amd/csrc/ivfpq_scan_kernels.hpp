@@ -17,10 +17,12 @@
  *   tiles; BS = GAMMA_SCAN_BS, or 256 where k2 + BS exceeds the selector cap.
  * - ksub 256, M in GAMMA_FAST_M, k2 + BS <= GAMMA_SORT_CAP
  *   (gamma_scan8_fast = gk::ivfpq_scan_builds_table): k_ivfpq_scan<IP, M/4,
- *   BS, RR>. Resident M*256 table built in-kernel (gamma_build_lut_l2 from
- *   codebooks + cwn, gamma_build_lut_ip). Chunked flat walk, prefetching
- *   pass loop (it stays in the kernel: scan_walk.hpp records why).
- * - ksub 256 otherwise: k_ivfpq_scan<IP, 0, WG, RR>. Resident table, L2
+ *   BS, RR, PR>. Resident M*256 table built in-kernel (gamma_build_lut_l2
+ *   from codebooks + cwn, gamma_build_lut_ip). Chunked flat walk,
+ *   prefetching pass loop (it stays in the kernel: scan_walk.hpp records
+ *   why). PR > 0 (L2, a pruning block, GAMMA_SCAN_PRUNE not 0): lists whose
+ *   distance bound exceeds the k2-th distance are skipped.
+ * - ksub 256 otherwise: k_ivfpq_scan<IP, 0, WG, RR, 0>. Resident table, L2
  *   copied from `atab` (pq_tables_a); gamma_pq_walk_lists, dword loads.
  * - ksub 16, M in GAMMA_FAST_M, k2 + BS*C <= GAMMA_SORT_CAP: k_ivfpq_scan4<IP,
  *   M/8, BS, C>. M*16 table (L2 from `atab`); two lists in flight per
@@ -345,11 +347,66 @@ struct GammaScanElem {
   bool live; /* false: the lane has no entry in this pass */
 };
 
+/* The list bound of the L2 fast path (DESIGN.md "Kernels" item 3 derives
+ * it). In exact arithmetic an entry's dis0 + S_v + sum_m T[m][code_m] is
+ * ||q - c - r||^2 >= (||q - c|| - ||r||)^2 with r its decoded residual, so
+ * no entry of a list lies below (sqrt(dis0) - rmax)^2 where sqrt(dis0) >
+ * rmax. The fp32 value the kernel computes differs from the exact one by
+ * less than eps * (||q|| + ||c|| + rmax)^2, the slack: the launcher sizes
+ * eps from d and M. The root is rounded down and the radius up by a
+ * relative 2^-20, which covers the roundings of this function itself. */
+struct GammaScanPruneArgs {
+  const float *rmax, *qnorms, *cnorms;
+  int *stats;
+  float eps;
+  int head; /* probes in the head chunk */
+};
+/* The kernel keeps the block in LDS behind the chunk (thread 0 copies it in
+ * front of the selector's first barrier): held as kernel arguments its six
+ * words stayed in SGPRs across the pass loop and pushed 17 of them into VGPR
+ * lanes. gamma_scan8_smem leaves the bytes out, so the kernel switch of
+ * gk::ivfpq_scan_is_wide does not move. */
+static size_t gamma_scan8_prune_smem(int M, int k2, int d) {
+  return gamma_scan8_smem(M, k2, d) + sizeof(GammaScanPruneArgs);
+}
+/* Whether list `ln`, probed by query row q at coarse distance dis0, holds
+ * no key below `thresh`. A NaN anywhere compares false: no skip.
+ * `size` is the list size just read from the bucket table, and the radius
+ * must not be older than it: the single-vector append raises the radius
+ * with a kernel, synchronises its stream, and only then writes the new size
+ * into the bucket table, so whatever memory level served a size already
+ * held that size's radius in the device-wide L2. What is relied on here:
+ * (1) the size load has RETURNED before the radius load is issued: the
+ * empty asm takes the loaded value as a register input, which makes the
+ * compiler wait for it (s_waitcnt vmcnt), and its memory clobber keeps the
+ * compiler from moving the radius load above it; (2) the radius load is an
+ * agent-scope atomic load, which is served by the L2 and never by a CU's
+ * L1, where a line fetched before the append could still sit. */
+__device__ __forceinline__ bool gamma_scan_list_skipped(
+    const GammaScanPruneArgs &pa, int q, int64_t ln, float dis0,
+    long long size, uint64_t thresh) {
+  if (thresh == GAMMA_KEY_EMPTY) return false;
+  asm volatile("" ::"v"((int)size) : "memory");
+  const float rm = __hip_atomic_load(pa.rmax + ln, __ATOMIC_RELAXED,
+                                     __HIP_MEMORY_SCOPE_AGENT) *
+                   (1.0f + 0x1p-20f);
+  const float gap = sqrtf(dis0) * (1.0f - 0x1p-20f) - rm;
+  if (!(gap > 0.0f)) return false;
+  const float lb = gap * gap * (1.0f - 0x1p-20f);
+  const float nrm = sqrtf(pa.qnorms[q]) + sqrtf(pa.cnorms[ln]) + rm;
+  const float kth = gamma_key_f32((uint32_t)(thresh >> 32));
+  return lb > kth + pa.eps * (nrm * nrm);
+}
+
 /* RR: the launch carries a re-rank block and ends in the epilogue of
  * rerank_epilogue.hpp instead of the out_keys store (S == 1 only). A
  * template flag, not a run-time test: the RR = false instantiations keep
- * the code they had before the epilogue existed. */
-template <bool IP, int MW, int BS, bool RR>
+ * the code they had before the epilogue existed.
+ * PR (L2 fast path only): 1 = the list bound above, behind a head chunk of
+ * pa.head probes and a forced flush; 2 = the same and the counters of
+ * pa.stats (kernel test hook). 0 = neither: the single walk in chunks of
+ * GAMMA_SCAN_PCH. */
+template <bool IP, int MW, int BS, bool RR, int PR>
 __global__ void __launch_bounds__(BS)
 k_ivfpq_scan(
     int nq, int S, int d, int M, int nprobe, int k2,
@@ -359,7 +416,8 @@ k_ivfpq_scan(
     const GammaBucketDev *__restrict__ buckets, int nlist,
     const int64_t *__restrict__ probes, const uint32_t *__restrict__ bitmap,
     uint64_t *__restrict__ out_keys, const int *__restrict__ kill_flag,
-    const int32_t *__restrict__ qmap, GammaScanRerank rr) {
+    const int32_t *__restrict__ qmap, GammaScanRerank rr,
+    GammaScanPruneArgs pa_arg) {
   extern __shared__ char smem[];
   const int ksub = 256;
   const int dsub = d / M;
@@ -370,11 +428,15 @@ k_ivfpq_scan(
   float *qs = (float *)(smem + gamma_pq_qs_off(ntab, k2)); /* d */
   GammaScanChunk *ch =
       (GammaScanChunk *)(smem + gamma_pq_chunk_off(ntab, k2, (size_t)d));
+  /* PR: the pruning block, in LDS behind the chunk (the launch adds the
+   * bytes); sel.init's barrier publishes it */
+  const GammaScanPruneArgs &pa = *(const GammaScanPruneArgs *)(ch + 1);
 
   const GammaScanBlock blk(S);
   if (blk.bq >= nq) return;
   const int sub = blk.sub;
   const int q = blk.query<true>(d, qmap, queries, qs);
+  if (PR && threadIdx.x == 0) *(GammaScanPruneArgs *)(ch + 1) = pa_arg;
 
   GammaSelector sel;
   sel.init(sortbuf, res, ch->state, k2);  /* has the barrier qs needs */
@@ -414,7 +476,12 @@ k_ivfpq_scan(
     const int *kf = kill_flag ? kill_flag : (const int *)probes;
     bool killed = false;
     for (int c0 = 0; c0 < np_sub && !killed;) {
-      const int cn = min(GAMMA_SCAN_PCH, np_sub - c0);
+      /* PR: probes arrive nearest first, so the first pa.head of them are
+       * a chunk of their own, closed by a forced flush: the later chunks
+       * then have a k2-th distance to hold their lists' bounds against */
+      const bool head_chunk = PR && c0 == 0;
+      const int cn =
+          min(head_chunk ? pa.head : GAMMA_SCAN_PCH, np_sub - c0);
       if ((int)tid < cn) { /* one thread per probe of the chunk */
         const int p = sub + (c0 + (int)tid) * S;
         const int64_t ln = probes[(int64_t)q * nprobe + p];
@@ -427,6 +494,21 @@ k_ivfpq_scan(
           else /* the coarse probe distance (ivfpq.h:255 dis0=coarse_dis); the
                   list half of the table arrives as the per-vector S term */
             dis0 = probe_dists[(int64_t)q * nprobe + p];
+          if (PR) {
+            /* sel.thresh is block-uniform and only ever falls: a list that
+             * cannot reach it now never will. Size 0 drops the list from
+             * the flat space like an empty one; nothing of it is loaded. */
+            const int cnt = (int)min(max(bk.size, 0ll), 0x7fffffffll);
+            if (PR == 2) atomicAdd(&pa.stats[3 * q + 2], cnt);
+            if (!head_chunk && gamma_scan_list_skipped(pa, q, ln, dis0,
+                                                       bk.size, sel.thresh)) {
+              if (PR == 2) {
+                atomicAdd(&pa.stats[3 * q], 1);
+                atomicAdd(&pa.stats[3 * q + 1], cnt);
+              }
+              bk = gamma_null_bucket();
+            }
+          }
         }
         gamma_pq_chunk_put(ch, tid, bk, dis0);
       }
@@ -521,8 +603,11 @@ k_ivfpq_scan(
       }
       /* barrier: the chunk is rewritten next round. It doubles as the
        * flush check an odd last pass skipped, so every chunk starts with
-       * a full margin. */
-      sel.maybe_flush(fmargin);
+       * a full margin. Behind the head chunk the flush is forced, unless
+       * the chunk held fewer than k2 entries: the threshold would stay
+       * EMPTY, and data that gains nothing is spared the sort. */
+      if (head_chunk && sp.total >= (unsigned)k2) sel.flush_now();
+      else sel.maybe_flush(fmargin);
     }
   } else {
     /* generic path: dword loads of the M/4 code words of an entry */
@@ -1048,6 +1133,32 @@ bool gk::ivfpq_scan_reads_table(int d, int M, int ksub, int k2, bool ip) {
 
 /* GAMMA_FUSE_RERANK=0 keeps re-rank and sort in kernels of their own
  * (A/B runs of one build, and tests that compare the two paths) */
+/* GAMMA_SCAN_PRUNE=0 keeps the L2 fast path's single walk without the list
+ * bound; GAMMA_SCAN_PRUNE_HEAD = probes in its head chunk (1..32) */
+static bool gamma_scan_prune() {
+  const char *e = getenv("GAMMA_SCAN_PRUNE");
+  return !(e && e[0] == '0' && e[1] == 0);
+}
+static int gamma_scan_prune_head() {
+  const char *e = getenv("GAMMA_SCAN_PRUNE_HEAD");
+  if (e && atoi(e) >= 1 && atoi(e) <= GAMMA_SCAN_PCH) return atoi(e);
+  return 2;
+}
+/* eps of the slack, relative to B = (||q|| + ||c|| + rmax)^2, which bounds
+ * the sum of the magnitudes of the M + 2 terms of an entry's chain. First
+ * order in u = 2^-24: the chain's M + 1 adds (M + 1) u B; a table entry is a
+ * dsub-term fmaf chain, its norm and one more rounding, (dsub + 1) u over
+ * all m; S_v is M adds of dsub-term chains, (M + dsub) u; the GEMM-form dis0
+ * is d products and two norms, (d + 2) u, and enters twice, as a term and
+ * under the root; the radius is M adds of dsub-term norms, (M + dsub + 2) u
+ * with its own root. Margin 8 on the total. */
+static float gamma_scan_prune_eps(int d, int M) {
+  const int dsub = d / M;
+  const int terms =
+      (M + 1) + (dsub + 1) + (M + dsub) + 2 * (d + 2) + (M + dsub + 2);
+  return 8.0f * (float)terms * 0x1p-24f;
+}
+
 static bool gamma_scan_fuse_rerank() {
   const char *e = getenv("GAMMA_FUSE_RERANK");
   return !(e && e[0] == '0' && e[1] == 0);
@@ -1070,7 +1181,8 @@ hipError_t gk::ivfpq_scan(
     const float *atab, const float *cwn, const float *probe_dists,
     const GammaBucketDev *buckets, int nlist, const int64_t *probes,
     const uint32_t *bitmap, bool ip, uint64_t *out_keys, const int *kill_flag,
-    const int32_t *qmap, const GammaScanRerank *rr) {
+    const int32_t *qmap, const GammaScanRerank *rr,
+    const GammaScanPrune *prune) {
   if (ksub != 256 && ksub != 16) return hipErrorInvalidValue;
   if (rr && (!gk::ivfpq_scan_can_fuse_rerank(d, M, ksub, k2, S) ||
              rr->k <= 0 || rr->k > GAMMA_SORT_CAP || !rr->queries ||
@@ -1100,24 +1212,46 @@ hipError_t gk::ivfpq_scan(
   if (ksub == 256) {
     const bool fast = gamma_scan8_fast(M, k2, BS);
     if (!ip && (fast ? !cwn : !atab)) return hipErrorInvalidValue;
-    const size_t smem = gamma_scan8_smem(M, k2, d);
+    size_t smem = gamma_scan8_smem(M, k2, d);
     if (smem > 160 * 1024) return hipErrorInvalidValue;
     const GammaScanRerank rrv = rr ? *rr : GammaScanRerank{};
+    /* the list bound: L2 fast path only, where its block still fits the
+     * LDS; the counting kernel exists without the re-rank epilogue only */
+    GammaScanPruneArgs pa = {};
+    int pr = 0;
+    if (prune && !ip && fast && gamma_scan_prune() &&
+        gamma_scan8_prune_smem(M, k2, d) <= 160 * 1024) {
+      smem = gamma_scan8_prune_smem(M, k2, d);
+      if (!prune->rmax || !prune->qnorms || !prune->cnorms ||
+          (prune->stats && rr))
+        return hipErrorInvalidValue;
+      pa = {prune->rmax, prune->qnorms, prune->cnorms, prune->stats,
+            gamma_scan_prune_eps(d, M), gamma_scan_prune_head()};
+      pr = prune->stats ? 2 : 1;
+    }
     gamma_pick<0, 1>(ip, [&](auto ipc) {
       gamma_pick<0, 1>(rr != nullptr, [&](auto rrc) {
-        auto launch = [&](auto mw, auto bs) {
-          constexpr bool IPV = decltype(ipc)::value;
-          constexpr bool RRV = decltype(rrc)::value;
+        constexpr bool IPV = decltype(ipc)::value;
+        constexpr bool RRV = decltype(rrc)::value;
+        auto launch = [&](auto mw, auto bs, auto prc) {
           constexpr int MWV = decltype(mw)::value, BSV = decltype(bs)::value;
-          k_ivfpq_scan<IPV, MWV, BSV, RRV><<<g, dim3(BSV), smem, s>>>(
-              nq, S, d, M, nprobe, k2, queries, centroids, codebooks, atab,
-              cwn, probe_dists, buckets, nlist, probes, bitmap, out_keys,
-              kill_flag, qmap, rrv);
+          k_ivfpq_scan<IPV, MWV, BSV, RRV, decltype(prc)::value>
+              <<<g, dim3(BSV), smem, s>>>(
+                  nq, S, d, M, nprobe, k2, queries, centroids, codebooks,
+                  atab, cwn, probe_dists, buckets, nlist, probes, bitmap,
+                  out_keys, kill_flag, qmap, rrv, pa);
         };
-        if (!fast) return launch(gamma_c<0>(), gamma_c<WG>());
+        if (!fast)
+          return launch(gamma_c<0>(), gamma_c<WG>(), gamma_c<0>());
         gamma_pick<GAMMA_FAST_M>(M, [&](auto m) {
           gamma_pick<256, 512>(BS, [&](auto bs) {
-            launch(gamma_c<decltype(m)::value / 4>(), bs);
+            const auto mw = gamma_c<decltype(m)::value / 4>();
+            if constexpr (!IPV) {
+              if (pr == 1) return launch(mw, bs, gamma_c<1>());
+              if constexpr (!RRV)
+                if (pr == 2) return launch(mw, bs, gamma_c<2>());
+            }
+            launch(mw, bs, gamma_c<0>());
           });
         });
       });

@@ -64,6 +64,19 @@ struct GammaScanRerank {
   int64_t *out_ids;         /* nq x k; -1 there */
 };
 
+/* pruning block of gk::ivfpq_scan (section 5 of its contract): per-list
+ * residual radii and the norms the rounding slack is sized by */
+struct GammaScanPrune {
+  const float *rmax;   /* nlist: >= the largest ||decoded residual|| of each
+                        * list's entries (gk::pq_list_rmax) */
+  const float *qnorms; /* nq: ||q||^2 of the scan's own queries, by
+                        * ORIGINAL row */
+  const float *cnorms; /* nlist: ||c||^2 */
+  int *stats;          /* kernel test hook only, else null: 3 ints per
+                        * query, zeroed by the caller: lists skipped,
+                        * entries skipped, entries of all valid probes */
+};
+
 namespace gk {
 
 /* Stable compaction of a batch of buckets in one launch, the mirror of
@@ -209,6 +222,20 @@ hipError_t pq_sterm(hipStream_t s, int64_t n, int M, int ksub, int nlist,
 hipError_t pq_sterm_buckets(hipStream_t s, int nlist, int M, int ksub,
                             const GammaBucketDev *bks, const float *btab);
 
+/* Per-list residual radius: rmax[ln] = max(rmax[ln], sqrt(sum_m
+ * cwn[m][code_m])) over the given entries, plain adds in ascending m: the
+ * norm of the decoded residual, which the scan's list bound needs (see
+ * ivfpq_scan, 5). The caller zeroes rmax once; later calls only raise it, so
+ * appends keep it an upper bound and deletes may leave it. Two forms:
+ *   bks != null: every entry of every bucket of bks[0, nlist), delete-marked
+ *                ones included (n, codes and asg are ignored);
+ *   bks == null: the n staged bucket-format entries `codes`, entry i in list
+ *                asg ? asg[i] : asg_const (outside [0, nlist): skipped). */
+hipError_t pq_list_rmax(hipStream_t s, int64_t n, int M, int ksub, int nlist,
+                        const uint8_t *codes, const int32_t *asg,
+                        int asg_const, const GammaBucketDev *bks,
+                        const float *cwn, float *rmax);
+
 /* IVFPQ fused search (the kernels are in ivfpq_scan_kernels.hpp).
  *
  * 1. What the launch computes. One workgroup per (query, probe-split
@@ -262,6 +289,8 @@ hipError_t pq_sterm_buckets(hipStream_t s, int nlist, int M, int ksub,
  *      8-bit fast path accepts and ignores it).
  *    - GAMMA_SCAN_WIDE=1 forces the wide kernel at any M.
  *    - GAMMA_FUSE_RERANK=0 turns ivfpq_scan_can_fuse_rerank off.
+ *    - GAMMA_SCAN_PRUNE=0 turns the list bound of 5 off;
+ *      GAMMA_SCAN_PRUNE_HEAD (1..32, default 2) is its head chunk.
  *
  * 4. Fused re-rank: with `rr` set the resident-table 8-bit kernel ends in
  *    the epilogue of rerank_epilogue.hpp — exact distances of the query's
@@ -270,7 +299,16 @@ hipError_t pq_sterm_buckets(hipStream_t s, int nlist, int M, int ksub,
  *    bit-identical to ivfpq_scan + rerank + sort_rows. Legal where
  *    ivfpq_scan_can_fuse_rerank: S == 1, 8-bit codes, not a wide launch,
  *    d % 4 == 0. Any other launch with rr set, or rr->k outside [1, 2048],
- *    is hipErrorInvalidValue and launches nothing. */
+ *    is hipErrorInvalidValue and launches nothing.
+ *
+ * 5. List bound: with `prune` set, an L2 launch of the table-building 8-bit
+ *    kernel (ivfpq_scan_builds_table) walks the first GAMMA_SCAN_PRUNE_HEAD
+ *    probes of each workgroup as a chunk of their own, flushes its selector,
+ *    and from then on skips every probed list with
+ *      (sqrt(dis0) - rmax[list])^2 > k2-th distance so far + rounding slack
+ *    (DESIGN.md "Kernels" item 3 has the bound and the slack). No entry of
+ *    such a list can enter the top-k2, so out_keys / the fused outputs are
+ *    bit-identical with and without it. Every other launch ignores `prune`. */
 enum { IVFPQ_WIDE_MS = 32, IVFPQ_WIDE_E = 4 };
 int ivfpq_wide_tile(); /* entries per tile at the current GAMMA_SCAN_BS */
 bool ivfpq_scan_is_wide(int d, int M, int ksub, int k2);
@@ -294,7 +332,8 @@ hipError_t ivfpq_scan(hipStream_t s, int nq, int S, int d, int M, int ksub,
                       int nlist, const int64_t *probes,
                       const uint32_t *bitmap, bool ip, uint64_t *out_keys,
                       const int *kill_flag, const int32_t *qmap,
-                      const GammaScanRerank *rr = nullptr);
+                      const GammaScanRerank *rr = nullptr,
+                      const GammaScanPrune *prune = nullptr);
 
 /* out[q] = (int32) probes[q*nprobe] (the schedule sort key) */
 hipError_t extract_probe0(hipStream_t s, int nq, int nprobe,

@@ -1566,6 +1566,58 @@ hipError_t gk::pq_sterm(hipStream_t s, int64_t n, int M, int ksub, int nlist,
   return hipGetLastError();
 }
 
+/* Per-list residual radius (gk::pq_list_rmax). bks != null: block b takes
+ * the entries of bucket b; else thread i takes staged entry i. Radii are
+ * non-negative floats, whose order is that of their bit patterns, so the
+ * per-list maximum is an integer atomicMax. */
+template <int KB>
+__global__ void k_pq_list_rmax(int64_t n, int M, int nlist,
+                               const uint8_t *__restrict__ codes,
+                               const int32_t *__restrict__ asg, int asg_const,
+                               const GammaBucketDev *__restrict__ bks,
+                               const float *__restrict__ cwn,
+                               float *__restrict__ rmax) {
+  const int eb = M * KB / 8;
+  if (bks) {
+    const GammaBucketDev bk = bks[blockIdx.x];
+    if (!bk.data || bk.size <= 0) return;
+    const uint8_t *c = (const uint8_t *)bk.data;
+    float v = 0.0f;
+    for (long long j = threadIdx.x; j < bk.size; j += blockDim.x)
+      v = fmaxf(v, gamma_sterm_sum<KB>(cwn, c + (size_t)j * eb, M));
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    if ((threadIdx.x & 63) == 0)
+      atomicMax((unsigned int *)rmax + blockIdx.x,
+                __float_as_uint(sqrtf(v)));
+    return;
+  }
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int ln = asg ? asg[i] : asg_const;
+  if (ln < 0 || ln >= nlist) return;
+  const float v = gamma_sterm_sum<KB>(cwn, codes + (size_t)i * eb, M);
+  atomicMax((unsigned int *)rmax + ln, __float_as_uint(sqrtf(v)));
+}
+
+hipError_t gk::pq_list_rmax(hipStream_t s, int64_t n, int M, int ksub,
+                            int nlist, const uint8_t *codes,
+                            const int32_t *asg, int asg_const,
+                            const GammaBucketDev *bks, const float *cwn,
+                            float *rmax) {
+  if (ksub != 256 && ksub != 16) return hipErrorInvalidValue;
+  if (!cwn || !rmax || nlist <= 0) return hipErrorInvalidValue;
+  if (!bks && n <= 0) return hipSuccess;
+  if (!bks && !codes) return hipErrorInvalidValue;
+  const dim3 g(bks ? (uint32_t)nlist : (uint32_t)((n + WG - 1) / WG));
+  if (ksub == 256)
+    k_pq_list_rmax<8><<<g, dim3(WG), 0, s>>>(n, M, nlist, codes, asg,
+                                             asg_const, bks, cwn, rmax);
+  else
+    k_pq_list_rmax<4><<<g, dim3(WG), 0, s>>>(n, M, nlist, codes, asg,
+                                             asg_const, bks, cwn, rmax);
+  return hipGetLastError();
+}
+
 /* ------------------------------------------------------ bucket scatter */
 __global__ void k_bucket_scatter(int nseg,
                                  const GammaScatterSeg *__restrict__ segs,

@@ -127,6 +127,15 @@ struct GammaSelector {
     flush_();
   }
 
+  /* An unconditional flush in the place of a maybe_flush (all threads
+   * together; the append counter restarts at 0, so the margin invariant
+   * holds behind it). Afterwards thresh is the true k-th key of everything
+   * pushed so far, or still GAMMA_KEY_EMPTY where fewer than k keys came. */
+  __device__ void flush_now() {
+    __syncthreads();
+    flush_();
+  }
+
  private:
   __device__ void flush_() {
     const int nt = blockDim.x, tid = threadIdx.x;

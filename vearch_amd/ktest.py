@@ -58,6 +58,12 @@ def _lib():
             i32, vp, vp, i32, i32, i32, vp, vp]
         L.GammaKTestIvfpqScanCanFuseRerank.argtypes = [
             i32, i32, i32, i32, i32]
+        L.GammaKTestIvfpqScanPrune.argtypes = [
+            i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp,
+            i32, vp, vp, i32, vp, vp, vp,
+            i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+        L.GammaKTestPqListRmax.argtypes = [
+            i64, i32, i32, i32, vp, vp, i32, vp, vp, vp]
         L.GammaKTestPqTablesIp.argtypes = [i32, i32, i32, vp, vp, vp]
         L.GammaKTestIvfpqWideInfo.argtypes = [
             i32, i32, i32, i32, c.POINTER(c.c_int)]
@@ -645,13 +651,76 @@ def ivfpq_scan_null_rerank(lists, probes, probe_dists, queries, centroids,
         ip, bitmap, qmap, kill_flag, None, ksub, "null"))
 
 
+def ivfpq_scan_prune(lists, probes, probe_dists, queries, centroids,
+                     codebooks, S, k2, bitmap=None, qmap=None, kill_flag=None,
+                     rmax=None, count=False, rerank=None):
+    """One L2 gk::ivfpq_scan launch (8-bit codes) WITH its pruning block,
+    under the current GAMMA_SCAN_PRUNE / GAMMA_SCAN_PRUNE_HEAD. rmax: float32
+    (nlist,) or None = gk::pq_list_rmax over the lists as uploaded; the norms
+    are gk::row_norms of queries and centroids. count: take the counting
+    kernel. rerank: None, or (base, seg_shift, k) as ivfpq_scan_rerank takes
+    them (not together with count). Returns (result, stats): result = keys
+    uint64 (nq, S, k2), or (dists, ids) with rerank; stats = None, or int32
+    (nq, 3): lists skipped, entries skipped, entries of all valid probes."""
+    rr = None
+    if rerank is not None:
+        base, seg_shift, k = rerank
+        rr = (np.ascontiguousarray(queries, dtype=np.float32),
+              split_segments(base, seg_shift), seg_shift, k)
+    res, stats = _ivfpq_scan_launch(
+        lists, probes, probe_dists, queries, centroids, codebooks, S, k2,
+        False, bitmap, qmap, kill_flag, None, 256, rr,
+        prune={"rmax": rmax, "count": bool(count)})
+    if rr is None:
+        return keys_to_np(res), stats
+    return (res[0].cpu().numpy(), res[1].cpu().numpy()), stats
+
+
+def pq_list_rmax(codes, cwn, M, ksub, nlist, asg=None, asg_const=0,
+                 buckets=None, rmax0=None):
+    """gk::pq_list_rmax on host arrays. cwn float32 (M, ksub). Staged form:
+    codes uint8 bucket entries (n, M) (packed (n, M/2) at ksub 16) with list
+    numbers asg int32 (n,) or asg_const. Bucket form: buckets = one entry
+    array per list (codes ignored). rmax0: the radii to raise (default
+    zeros). -> float32 (nlist,) numpy."""
+    eb = M if ksub == 256 else M // 2
+    w_d = _f32_dev(cwn)
+    assert w_d.numel() == M * ksub
+    r_d = _f32_dev(np.zeros(nlist, np.float32) if rmax0 is None else rmax0)
+    assert r_d.shape == (nlist,)
+    if buckets is not None:
+        assert len(buckets) == nlist
+        keep, rows = [], []
+        for ent in buckets:
+            ent = np.ascontiguousarray(ent, dtype=np.uint8)
+            n = ent.shape[0]
+            assert ent.shape == (n, eb)
+            e_d = _u8_dev(ent)
+            keep.append(e_d)
+            rows.append([0, e_d.data_ptr() if n else 0, 0, n])
+        bk_d = torch.tensor(rows, dtype=torch.int64).reshape(-1, 4).cuda()
+        _call("GammaKTestPqListRmax", 0, M, ksub, nlist, None, None, 0,
+              _p(bk_d, torch.int64), _p(w_d), _p(r_d))
+        return r_d.cpu().numpy()
+    codes = np.ascontiguousarray(codes, dtype=np.uint8)
+    n = codes.shape[0]
+    assert codes.shape == (n, eb)
+    c_d = _u8_dev(codes)
+    a_d = None if asg is None else _i32_dev(asg)
+    assert a_d is None or a_d.shape == (n,)
+    _call("GammaKTestPqListRmax", n, M, ksub, nlist, _p(c_d),
+          _p(a_d, torch.int32), asg_const, None, _p(w_d), _p(r_d))
+    return r_d.cpu().numpy()
+
+
 def _ivfpq_scan_launch(lists, probes, probe_dists, queries, centroids,
                        codebooks, S, k2, ip, bitmap, qmap, kill_flag,
-                       code_offsets, ksub, rr):
+                       code_offsets, ksub, rr, prune=None):
     """The launch behind ivfpq_scan (rr None: returns the (nq, S, k2) key
     tensor) and ivfpq_scan_rerank (rr = (raw queries, segments, seg_shift,
     k): returns the (dists, ids) tensors; the key tensor is checked to be
-    untouched)."""
+    untouched). prune = {"rmax", "count"}: the launch carries the pruning
+    block (ivfpq_scan_prune) and the return value is (that, stats)."""
     f32 = lambda a: torch.from_numpy(  # noqa: E731
         np.ascontiguousarray(a, dtype=np.float32).copy()).cuda()
     q_d, cent_d, cb_d = f32(queries), f32(centroids), f32(codebooks)
@@ -715,6 +784,37 @@ def _ivfpq_scan_launch(lists, probes, probe_dists, queries, centroids,
             _p(bk_d, torch.int64), nlist, _p(pr_d, torch.int64),
             _p(bm_d, torch.int32), int(bool(ip)), _p(keys, torch.int64),
             _p(kf_d, torch.int32), _p(qm_d, torch.int32))
+    if prune is not None:
+        assert ksub == 256 and not ip and rr != "null"
+        if prune["rmax"] is None:
+            rm_d = torch.zeros((nlist,), dtype=torch.float32, device="cuda")
+            _call("GammaKTestPqListRmax", 0, M, 256, nlist, None, None, 0,
+                  _p(bk_d, torch.int64), _p(cwn), _p(rm_d))
+        else:
+            rm_d = f32(prune["rmax"])
+        assert rm_d.shape == (nlist,)
+        qn_d = torch.full((nq,), float("nan"), dtype=torch.float32,
+                          device="cuda")
+        cn_d = torch.full((nlist,), float("nan"), dtype=torch.float32,
+                          device="cuda")
+        _call("GammaKTestRowNorms", _p(q_d), nq, d, _p(qn_d))
+        _call("GammaKTestRowNorms", _p(cent_d), nlist, d, _p(cn_d))
+        st_d = torch.zeros((nq, 3), dtype=torch.int32, device="cuda") \
+            if prune["count"] else None
+        pargs = (_p(rm_d), _p(qn_d), _p(cn_d), _p(st_d, torch.int32))
+        stats = lambda: None if st_d is None else st_d.cpu().numpy()  # noqa: E731,E501
+        if rr is None:
+            _call("GammaKTestIvfpqScanPrune", *args, 0, None, None, 0, 0, 0,
+                  None, None, *pargs)
+            return keys, stats()
+        rq, segs, seg_shift, k = rr
+        rq_d = f32(rq)
+        table = seg_table(segs)
+        od = torch.full((nq, k), -7.0, dtype=torch.float32, device="cuda")
+        oi = torch.full((nq, k), -7, dtype=torch.int64, device="cuda")
+        _call("GammaKTestIvfpqScanPrune", *args, 1, _p(rq_d), _p(table),
+              len(segs), seg_shift, k, _p(od), _p(oi), *pargs)
+        return (od, oi), stats()
     if rr is None:
         _call("GammaKTestIvfpqScan", *args)
         return keys
