@@ -320,20 +320,23 @@ BITMAP_CAND_BLOCK = 8192  # ids per compaction block (kernels.h)
 
 def bitmap_candidates(words_u32, n, cap=None):
     """gk::bitmap_candidates: exclusion bitmap (numpy uint32 words) over ids
-    [0, n) -> (ids numpy uint32 of length cap, count). cap defaults to n;
-    slots the kernel did not write keep the fill 0xA5A5A5A5."""
+    [0, n) -> (ids numpy uint32, count). cap defaults to n; slots the kernel
+    did not write keep the fill 0xA5A5A5A5. The array has max(cap, n, 1)
+    slots, all returned: the kernel owns the first cap of them, and with
+    cap < n the rest show a store past cap (at most n ids exist, so such a
+    store stays inside the allocation)."""
     cap = n if cap is None else cap
     words = np.ascontiguousarray(words_u32, dtype=np.uint32)
     assert words.shape[0] * 32 >= n
     bm = bitmap_to_dev(words) if words.shape[0] else None
-    out = torch.full((max(cap, 1),), 0xA5A5A5A5 - (1 << 32),
+    out = torch.full((max(cap, n, 1),), 0xA5A5A5A5 - (1 << 32),
                      dtype=torch.int32, device="cuda")
     nblk = (n + BITMAP_CAND_BLOCK - 1) // BITMAP_CAND_BLOCK
     tmp = torch.full((max(nblk, 1),), -7, dtype=torch.int32, device="cuda")
     count = torch.full((1,), -7, dtype=torch.int32, device="cuda")
     _call("GammaKTestBitmapCandidates", _p(bm, torch.int32), n, _p(out), cap,
           _p(tmp), _p(count))
-    return out.cpu().numpy().view(np.uint32)[:cap], int(count.item())
+    return out.cpu().numpy().view(np.uint32), int(count.item())
 
 
 def cand_scan(queries, segs, seg_shift, ip, cand_u32, ncand_pad=None):
